@@ -2,7 +2,7 @@
 """
 bench.py -- headline benchmark of the MI355X ReFeX / RolX hot path.
 
-    python bench.py --gpus 1 --steps K --warmup W [--workload ba1m|er100k|ba100k|tiny]
+    python bench.py --gpus 1 --steps K --warmup W [--workload ba1m|er100k|ba100k|tiny] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,11 +12,19 @@ max_generations=4) followed by RolX NMF (NNDSVDa + multiplicative updates to con
 n_roles=6) on the resulting features, device-to-device.  The timed region is K steps between
 barrier + synchronize pairs; the time is the max over ranks.
 
+A plain run sets up, runs W warm-up steps, times the K steps and prints one JSON line with the headline figures
+(value, ms_per_step, refex, nmf).  --dump-outputs DIR then writes what the last timed step computed, as a caller of
+the path receives it (dump_outputs below).  --full adds everything else the line used to carry: the per-kernel
+breakdown, the event-free re-timing, the soak loop, encode / RolX / API wall-clock figures, the rooflines (with the
+rocprofv3 --pmc passes), the CPU baselines and, for N > 1, per-rank figures and the extra sharded config-5 line.
+
   value            = edges aggregated per second of the WHOLE step = nnz * executed recursive
                      generations * K / (time of the K timed steps, ReFeX pass + NMF), whole job
   refex.edges_per_s = the same numerator over the time spent in the ReFeX phase only
   nmf.iters_per_s  = multiplicative-update iterations / s over the NMF phase of the same steps
   ms_per_step      = whole step (both phases)
+
+--full only:
   ms_per_step_without_launch_events = the same K steps timed once more with the per-launch HIP events of the
                      timed region switched off (reported next to ms_per_step, never instead of it)
   roofline_nmf     = the NMF W pass; its launch time comes from the untimed breakdown pass (events
@@ -38,7 +46,7 @@ barrier + synchronize pairs; the time is the max over ranks.
 With --gpus N > 1 the same graph is node-range sharded over the ranks (strong scaling): grx_refex_run and
 grx_nmf_fit take the run's communicator (csrc/grx_comm.hip: RCCL bound inside libgrx.so) and issue the exchanges
 themselves -- per generation the candidate row slices go to the column owners, bins come back, and only the
-retained columns are completed on every rank; one all-reduce per NMF iteration.  The line then also carries
+retained columns are completed on every rank; one all-reduce per NMF iteration.  With --full the line then also carries
 `sharded_dw5m`: the same measurement on BASELINE config 5 (5 M nodes / 100 M weighted arcs), the workload where
 sharding pays (90 ms per step on one GPU).  `per_rank` lists every rank's aggregation launch time and the device
 time of its exchanges by kind.
@@ -481,6 +489,31 @@ def api_wall(G, args, reps=3, with_roles=True):
     return out
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs writes at most this much (a seeded sample of rows above it)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, K, fe, G, state):
+    """--dump-outputs: what one timed step computed, as a caller of the path receives it, as float64 .npy files:
+      features.npy             [s, F]  rows of the feature table (extract_features(): label order, columns in output order)
+      node_role_factor.npy     [s, r]  the same rows of the NMF node-role factor (W)
+      role_feature_factor.npy  [r, F]  the role-feature factor (H), whole
+    s = n when the three fit in DUMP_BYTES, else a fixed sample of rows (seed DUMP_SEED, ascending label order), so
+    that two builds run with the same arguments can be compared file for file."""
+    n, F, r = G.n, state['F'], N_ROLES
+    rows = max(1, (DUMP_BYTES - r * F * 8) // ((F + r) * 8))
+    pick = np.arange(n) if n <= rows else np.sort(np.random.default_rng(DUMP_SEED).choice(n, rows, replace=False))
+    host = fe.graph._device_graph()[0]
+    index = K.to_device(np.ascontiguousarray(host.inv[pick], dtype=np.int32))      # label row -> internal row
+    Xd, W = state['Xd'], state['W']
+    X = K.to_host(K.permute_columns([Xd[c] for c in range(F)], index, len(pick)).contiguous())
+    Wl = K.to_host(K.permute_columns([W[k] for k in range(r)], index, len(pick)).contiguous())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'features.npy'), np.ascontiguousarray(X.T, dtype=np.float64))
+    np.save(os.path.join(out_dir, 'node_role_factor.npy'), np.ascontiguousarray(Wl.T, dtype=np.float64))
+    np.save(os.path.join(out_dir, 'role_feature_factor.npy'), np.ascontiguousarray(K.to_host(state['H']), dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -501,24 +534,35 @@ def main():
     ap.add_argument('--cpu-nmf', type=int, default=1)
     ap.add_argument('--pmc', default='auto', choices=['auto', 'on', 'off'],
                     help='same-run hardware counters: re-run two steps under rocprofv3 --pmc (one pass per counter group) '
-                         'and fold HBM traffic / L2 hit rate / MFMA busy into the line; auto = when N = 1 and rocprofv3 exists')
+                         'and fold HBM traffic / L2 hit rate / MFMA busy into the line (--full only); auto = when N = 1 and rocprofv3 exists')
     ap.add_argument('--pmc-child', action='store_true', help='internal: the process a --pmc pass profiles (two steps, no output)')
     ap.add_argument('--soak-seconds', type=float, default=2.5,
                     help='after the timed region: keep stepping (untimed) for this long so that an external GPU-activity '
                          'sampler sees the device busy; 0 disables')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline figures: per-kernel breakdown, event-free re-timing, soak, '
+                         'encode / RolX / API wall-clock, rooflines and counter passes, CPU baselines, per-rank figures '
+                         'and the sharded config-5 line (N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed as DIR/<name>.npy (float64)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, rendezvous on the
-        # loopback address -- the container hostname may not resolve)
+        # `python bench.py --gpus N` without a launcher: start the launcher as a child (one rank per GPU, rendezvous on
+        # the loopback address -- the container hostname may not resolve) and exit with its status
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(('127.0.0.1', 0))
             port = sock.getsockname()[1]
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
                '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
 
     import torch
     import torch.distributed as dist
@@ -548,8 +592,9 @@ def main():
     import shutil
     have_rocprof = bool(shutil.which('rocprofv3') or os.path.exists('/opt/rocm/bin/rocprofv3'))
     under_profiler = any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)
-    use_pmc = (not args.pmc_child and world == 1 and not multi and
+    use_pmc = (args.full and not args.pmc_child and world == 1 and not multi and
                (args.pmc == 'on' or (args.pmc == 'auto' and have_rocprof and not under_profiler)))
+    full = args.full
 
     def run_workload(workload, steps, warmup, light):
         """One measured workload; light = the extra sharded line of an N > 1 run (no breakdown pass, no CPU legs)."""
@@ -599,7 +644,7 @@ def main():
             timers['nmf'] += t2 - t1
             timers['nmf_iters'] += n_iter
             state.update(names=names, Xd=Xd, n_iter=n_iter, gens=fe.generation_count, stats=list(fe.stats),
-                         F=len(names), W=nmf_state.W)
+                         F=len(names), W=nmf_state.W, H=nmf_state.H)
 
         warm = dict(refex=0.0, nmf=0.0, nmf_iters=0)
         if args.pmc_child:                              # the process a counter pass profiles: two plain steps
@@ -609,14 +654,17 @@ def main():
             return None
         for _ in range(warmup):
             step(warm)
-        # untimed breakdown pass: HIP events around EVERY kernel launch (per-kernel ms per step)
-        lib.grx_profile_reset()
-        lib.grx_profile_select(0)
-        lib.grx_profile_enable(1)
-        step(dict(refex=0.0, nmf=0.0, nmf_iters=0))
-        torch.cuda.synchronize()
-        breakdown = profile_totals(lib)
-        # timed region: events only around the kernel the `roofline` object is about
+        breakdown = {}
+        if full:
+            # untimed breakdown pass: HIP events around EVERY kernel launch (per-kernel ms per step)
+            lib.grx_profile_reset()
+            lib.grx_profile_select(0)
+            lib.grx_profile_enable(1)
+            step(dict(refex=0.0, nmf=0.0, nmf_iters=0))
+            torch.cuda.synchronize()
+            breakdown = profile_totals(lib)
+        # timed region: events only around the kernel the `roofline` object is about (a plain run times the same
+        # region, so that its ms_per_step is the figure of a --full run)
         names = {lib.grx_profile_kernel_name(i).decode(): i for i in range(lib.grx_profile_kernel_count())}
         mask = 0
         # (only the dominant kernel: every event record costs the host about as much as a launch, and twenty W-pass
@@ -626,6 +674,7 @@ def main():
             mask |= 1 << names[kname]
         lib.grx_profile_reset()
         lib.grx_profile_select(mask)
+        lib.grx_profile_enable(1)
         timers = dict(refex=0.0, nmf=0.0, nmf_iters=0)
         barrier()
         t_start = time.perf_counter()
@@ -634,21 +683,25 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t_start
         lib.grx_profile_enable(0)
-        prof = profile_totals(lib)
+        if args.dump_outputs and rank == 0 and not light:
+            dump_outputs(args.dump_outputs, K, fe, G, state)
+        prof = profile_totals(lib) if full else {}
         # the same steps once more WITHOUT the per-launch events of the timed region (what a caller runs: no event
         # records between the small launches) -- reported next to `value`,
         # never instead of it
-        plain = dict(refex=0.0, nmf=0.0, nmf_iters=0)
-        barrier()
-        t_plain = time.perf_counter()
-        for _ in range(steps):
-            step(plain)
-        barrier()
-        t_plain = time.perf_counter() - t_plain
+        t_plain = None
+        if full:
+            plain = dict(refex=0.0, nmf=0.0, nmf_iters=0)
+            barrier()
+            t_plain = time.perf_counter()
+            for _ in range(steps):
+                step(plain)
+            barrier()
+            t_plain = time.perf_counter() - t_plain
         # the cold API pairs, first set: right after the timed region (before the soak loop and the counter passes, whose
         # influence on the host side of the calls the second set below makes visible)
         api_before = None
-        if rank == 0 and world == 1 and not args.no_api_wall and not light:
+        if full and rank == 0 and world == 1 and not args.no_api_wall and not light:
             try:
                 api_before = api_wall(G, args, reps=3, with_roles=False)
             except Exception as exc:
@@ -658,7 +711,7 @@ def main():
         soak = None
         # (N = 1 only: the loop is bounded by TIME, and ranks that ran different step counts would leave each other
         # waiting inside an exchange)
-        if args.soak_seconds > 0 and not light and not multi:
+        if full and args.soak_seconds > 0 and not light and not multi:
             t_soak, n_soak = time.perf_counter(), 0
             while time.perf_counter() - t_soak < args.soak_seconds:
                 step(dict(refex=0.0, nmf=0.0, nmf_iters=0))
@@ -667,7 +720,7 @@ def main():
             soak = {'seconds': time.perf_counter() - t_soak, 'steps': n_soak, 'what': 'untimed steps after the timed region'}
         # N > 1: one more (untimed) step with HIP events around every exchange -> exchange share of a step
         exchange = None
-        if plan is not None:
+        if full and plan is not None:
             plan.reset_timing()
             plan.timing = True
             barrier()
@@ -688,7 +741,7 @@ def main():
         elapsed, t_refex, t_nmf = [float(x) for x in red.cpu()]
         # N > 1 soak: bounded by a STEP COUNT every rank derives from the same reduced time (a time-bounded loop would
         # leave ranks that ran different counts waiting inside an exchange) -- an external sampler sees N busy devices
-        if args.soak_seconds > 0 and not light and multi:
+        if full and args.soak_seconds > 0 and not light and multi:
             n_soak = max(1, min(2000, int(np.ceil(args.soak_seconds / max(elapsed / steps, 1e-6)))))
             t_soak = time.perf_counter()
             for _ in range(n_soak):
@@ -700,7 +753,7 @@ def main():
         # RolX encode of the node-role factor, outside the timed steps: the reference's quantiser reproduced
         # (grx_kmeans1d, the default of RoleExtractor) and the Lloyd-Max solver (quantizer='lloyd_max')
         encode_info = None
-        if rank == 0 and world == 1 and not light:
+        if full and rank == 0 and world == 1 and not light:
             Wd = state['W']
             n_bins = 2 ** int(np.log2(N_ROLES * min(G.n, state['F'])))          # roles/extract.py:72
             flat = K.transpose(Wd, N_ROLES, G.n).reshape(-1)                      # the reference's flatten order (n x r)
@@ -718,7 +771,7 @@ def main():
         # RolX's real cost per call (roles/extract.py:59-93,144-161): NMF fit + encode(G) + encode(F) on the same device
         # table the steps factorise, as RoleExtractor(n_roles=6).extract_role_factors runs them -- outside `value`
         rolx_info = None
-        if rank == 0 and world == 1 and not light:
+        if full and rank == 0 and world == 1 and not light:
             try:
                 n_bits = int(np.log2(N_ROLES * min(G.n, state['F'])))               # roles/extract.py:72
                 shape = (G.n, state['F'])
@@ -739,7 +792,7 @@ def main():
 
         # per-rank figures (N > 1): every rank's aggregation launch time and exchange time, gathered on rank 0
         per_rank = None
-        if multi:
+        if full and multi:
             agg_ms_r, agg_cnt_r = prof.get('aggregate_kernel', (0.0, 0))
             hub_ms_r, _ = prof.get('aggregate_hub_kernel', (0.0, 0))
             w_ms_r, w_cnt_r = breakdown.get('nmf_w_pass_kernel', (0.0, 0))
@@ -858,7 +911,6 @@ def main():
                 'metric': 'ReFeX edges-aggregated/sec (+ RolX NMF iters/sec in nmf.iters_per_s), 1M-node graph',
                 'value': value, 'unit': 'edges/s', 'n_gpus': world, 'steps': steps, 'warmup': warmup,
                 'ms_per_step': elapsed / steps * 1e3, 'higher_is_better': True, 'scaling': 'strong',
-                'ms_per_step_without_launch_events': t_plain / steps * 1e3,
                 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
                 'config': {'workload': args_workload, 'description': WORKLOADS[args_workload][3], 'n_nodes': G.n,
                            'n_edges': G.num_edges, 'nnz': G.nnz, 'max_generations': MAX_GENERATIONS,
@@ -872,9 +924,13 @@ def main():
                           'generations': state['stats']},
                 'nmf': {'iters_per_s': timers['nmf_iters'] / t_nmf, 'ms_per_step': t_nmf / steps * 1e3,
                         'iterations_per_step': state['n_iter'], 'includes': 'NNDSVDa init + MU loop + convergence checks'},
-                'soak': soak, 'encode': encode_info, 'rolx': rolx_info, 'roofline': roofline, 'roofline_nmf': roofline_nmf,
-                'kernel_ms_per_step': {k: v[0] for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1][0])},
             }
+            if full:
+                line.update({
+                    'ms_per_step_without_launch_events': t_plain / steps * 1e3,
+                    'soak': soak, 'encode': encode_info, 'rolx': rolx_info, 'roofline': roofline, 'roofline_nmf': roofline_nmf,
+                    'kernel_ms_per_step': {k: v[0] for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1][0])},
+                })
             if per_rank is not None:
                 # per-rank roofline of the aggregation kernel (each rank owns ~1/N of the rows and of the nnz) and the
                 # share of a step spent in exchanges: what a scaling curve has to be read against
@@ -889,7 +945,7 @@ def main():
             # the cold API calls come FIRST: the CPU legs below (pandas / networkx / sklearn, their thread pools and
             # multi-GB temporaries) leave the process in a state in which the 4.6 GB result table of dw5m takes 1.3 s
             # instead of 0.3 s to materialise -- not what a user of the two calls sees
-            if world == 1 and not args.no_api_wall and not light:
+            if full and world == 1 and not args.no_api_wall and not light:
                 try:
                     line['api_wall_s'] = api_wall(G, args, reps=3)
                     line['api_wall_s']['when'] = 'after the soak loop and the rocprofv3 --pmc child processes'
@@ -898,7 +954,7 @@ def main():
                 except Exception as exc:
                     line['api_wall_s'] = {'error': repr(exc)}
                 line['api_wall_before_soak_s'] = api_before
-            if world == 1 and not args.no_cpu_baseline and not light:
+            if full and world == 1 and not args.no_cpu_baseline and not light:
                 Xh = K.to_host(state['Xd'])[:, :G.n].T.copy() if args.cpu_nmf else None
                 base, extra = cpu_baseline(G, args, Xh)
                 line['cpu_baseline'] = base
@@ -914,7 +970,7 @@ def main():
         return None
 
     line = run_workload(args.workload, args.steps, args.warmup, light=False)
-    if multi and not args.no_sharded_extra and args.workload != 'dw5m':
+    if full and multi and not args.no_sharded_extra and args.workload != 'dw5m':
         # the workload where sharding pays (BASELINE config 5: 90 ms per step on one GPU), beside the headline
         extra = run_workload('dw5m', max(2, min(args.steps, 5)), 1, light=True)
         if rank == 0 and extra is not None:

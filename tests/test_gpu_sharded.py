@@ -140,7 +140,7 @@ def test_bench_launches_itself_on_two_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     env['GRX_BENCH_SHARE_GPU'] = '1'
     proc = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', 'ba100k', '--steps', '2',
-                           '--warmup', '1', '--no-sharded-extra'], capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
+                           '--warmup', '1', '--no-sharded-extra', '--full'], capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, proc.stdout[-2000:]

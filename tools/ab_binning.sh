@@ -3,9 +3,9 @@ OUT=gpurun_out/a8; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_kernels.py -q -m gpu -x -k "log_bin or chebyshev" 2>&1 | tail -12
 GRX_BIN_SORT=1 timeout 900 python -m pytest tests/test_gpu_kernels.py -q -m gpu -x -k "log_bin or chebyshev" 2>&1 | tail -4
 for v in 0 1; do
-  GRX_BIN_SORT=$v timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-api-wall > $OUT/bench_$v.json 2> $OUT/bench_$v.err
-  GRX_BIN_SORT=$v timeout 300 python bench.py --workload er100k --steps 20 --warmup 5 --no-cpu-baseline --no-api-wall > $OUT/er_$v.json 2> $OUT/er_$v.err
-  GRX_BIN_SORT=$v timeout 600 python bench.py --workload dw5m --steps 4 --warmup 2 --no-cpu-baseline --no-api-wall > $OUT/dw_$v.json 2> $OUT/dw_$v.err
+  GRX_BIN_SORT=$v timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-api-wall > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  GRX_BIN_SORT=$v timeout 300 python bench.py --full --workload er100k --steps 20 --warmup 5 --no-cpu-baseline --no-api-wall > $OUT/er_$v.json 2> $OUT/er_$v.err
+  GRX_BIN_SORT=$v timeout 600 python bench.py --full --workload dw5m --steps 4 --warmup 2 --no-cpu-baseline --no-api-wall > $OUT/dw_$v.json 2> $OUT/dw_$v.err
 done
 python - <<PY
 import json

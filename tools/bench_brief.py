@@ -1,4 +1,4 @@
-"""stdin: bench.py's JSON line -> the few figures one looks at between two builds."""
+"""stdin: the JSON line of bench.py --full -> the few figures one looks at between two builds."""
 import json
 import sys
 

@@ -10,5 +10,5 @@ bash tools/final_lines.sh > $OUT/final_lines.log 2>&1; tail -8 $OUT/final_lines.
 bash tools/prof_kmeans.sh f6 6000000 64 > $OUT/pk_f6.txt 2>&1; bash tools/prof_kmeans.sh f30 30000000 512 > $OUT/pk_f30.txt 2>&1
 timeout 900 python tools/project_scaling.py ba1m 2> $OUT/proj_ba1m.err | tail -1 > $OUT/projected_scaling_ba1m.json; python tools/show_projection.py $OUT/projected_scaling_ba1m.json | grep '^P'
 timeout 300 python tools/time_triangle_slices.py ba1m 8 > $OUT/triangle_slices.txt 2>&1
-timeout 600 python bench.py --workload ba10m --steps 3 --warmup 1 --no-cpu-baseline --no-api-wall > $OUT/bench_ba10m.json 2> $OUT/bench_ba10m.err; tail -c 300 $OUT/bench_ba10m.err
+timeout 600 python bench.py --full --workload ba10m --steps 3 --warmup 1 --no-cpu-baseline --no-api-wall > $OUT/bench_ba10m.json 2> $OUT/bench_ba10m.err; tail -c 300 $OUT/bench_ba10m.err
 du -sh gpurun_out
