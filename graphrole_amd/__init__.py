@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == 'RoleExtractor':
         from .roles.extract import RoleExtractor
         return RoleExtractor
+    if name in ('node_measures', 'ConvergenceError'):
+        from . import measures
+        return getattr(measures, name)
     raise AttributeError(name)

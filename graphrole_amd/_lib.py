@@ -29,6 +29,15 @@ class GrxDegenerate(GrxError, ValueError):
     """GRX_ERR_DEGENERATE: numerically degenerate input (an all-zero feature matrix)."""
 
 
+class ConvergenceError(GrxError):
+    """GRX_ERR_NOT_CONVERGED: a power iteration did not converge within max_iter iterations (networkx raises
+    PowerIterationFailedConvergence).  ``iterations``: how many ran."""
+
+    def __init__(self, message: str, iterations: int = 0):
+        super().__init__(message)
+        self.iterations = int(iterations)
+
+
 class NmfInfo(ctypes.Structure):
     """grx_nmf_info of include/grx.h."""
     _fields_ = [('n_iter', c_int), ('direct_residuals', c_int), ('err_init', c_double), ('err_last', c_double),
@@ -226,6 +235,15 @@ _SIGNATURES = {
     'grx_row_normalise': (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     'grx_nmf_iterate': (c_int, [c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'grx_pagerank_workspace_bytes': (c_size_t, [c_int64]),
+    'grx_pagerank': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double,
+                             c_double, c_int, c_void_p, POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    'grx_eigenvector_centrality_workspace_bytes': (c_size_t, [c_int64]),
+    'grx_eigenvector_centrality': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double,
+                                           c_int, c_void_p, POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    'grx_local_structure_measures': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    'grx_host_nnls': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -259,6 +277,8 @@ def check(status: int, what: str = '') -> None:
         raise GrxInvalid(text)
     if status == -5:
         raise GrxDegenerate(text)
+    if status == -6:
+        raise ConvergenceError(text)
     raise GrxError(f'[status {status}] {text}')
 
 

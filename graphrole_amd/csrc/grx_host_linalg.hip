@@ -648,3 +648,140 @@ int grx_host_nndsvd_plan(int r, int F, const double *S, const double *Vt, const 
 }
 
 }  // extern "C"
+
+namespace {
+
+// ---- NNLS of RolX sense making (grx_host_nnls) -------------------------------------------------------------------
+
+// Cholesky L L^T of A[P][P] (P in the order the variables became passive, so a dependent newcomer fails last):
+// -1, or the position in P of the first pivot that lost all but a 1e-12 share of its diagonal (dependent column)
+int nnls_cholesky(int r, const double *A, const std::vector<int> &P, std::vector<double> &L)
+{
+    const int k = (int)P.size();
+    L.assign((size_t)k * k, 0.0);
+    for (int j = 0; j < k; ++j) {
+        const double ajj = A[(size_t)P[j] * r + P[j]];
+        double d = ajj;
+        for (int l = 0; l < j; ++l) d -= L[(size_t)j * k + l] * L[(size_t)j * k + l];
+        if (!(d > 1e-12 * ajj) || !(d > 0.0)) return j;
+        const double ljj = std::sqrt(d);
+        L[(size_t)j * k + j] = ljj;
+        for (int i = j + 1; i < k; ++i) {
+            double v = A[(size_t)P[i] * r + P[j]];
+            for (int l = 0; l < j; ++l) v -= L[(size_t)i * k + l] * L[(size_t)j * k + l];
+            L[(size_t)i * k + j] = v / ljj;
+        }
+    }
+    return -1;
+}
+
+// one column: min_{x >= 0} x^T A x - 2 b^T x (Lawson & Hanson, Solving Least Squares Problems, ch. 23)
+void nnls_column(int r, const double *A, const double *b, double tol, double *x)
+{
+    std::vector<char> passive(r, 0), excluded(r, 0);
+    std::vector<int> P;
+    std::vector<double> L, z(r), y(r), w(r);
+    for (int i = 0; i < r; ++i) x[i] = 0.0;
+    auto gradient = [&]() {                                        // w = b - A x
+        for (int i = 0; i < r; ++i) {
+            double v = b[i];
+            for (int l = 0; l < r; ++l) v -= A[(size_t)i * r + l] * x[l];
+            w[i] = v;
+        }
+    };
+    gradient();
+    const int max_outer = 3 * r + 10;
+    for (int outer = 0; outer < max_outer; ++outer) {
+        int t = -1;
+        double best = tol;
+        for (int i = 0; i < r; ++i)
+            if (!passive[i] && !excluded[i] && w[i] > best) { best = w[i]; t = i; }
+        if (t < 0) break;
+        passive[t] = 1;
+        P.push_back(t);
+        for (int inner = 0; inner < max_outer && !P.empty(); ++inner) {
+            const int fail = nnls_cholesky(r, A, P, L);
+            if (fail >= 0) {                                       // dependent on the passive columns before it
+                const int d = P[fail];
+                passive[d] = 0;
+                excluded[d] = 1;
+                x[d] = 0.0;
+                P.erase(P.begin() + fail);
+                continue;
+            }
+            const int k = (int)P.size();
+            for (int i = 0; i < k; ++i) {                          // L y = b_P, L^T z = y
+                double v = b[P[i]];
+                for (int l = 0; l < i; ++l) v -= L[(size_t)i * k + l] * y[l];
+                y[i] = v / L[(size_t)i * k + i];
+            }
+            for (int i = k - 1; i >= 0; --i) {
+                double v = y[i];
+                for (int l = i + 1; l < k; ++l) v -= L[(size_t)l * k + i] * z[l];
+                z[i] = v / L[(size_t)i * k + i];
+            }
+            bool feasible = true;
+            for (int i = 0; i < k; ++i) feasible = feasible && z[i] > 0.0;
+            if (feasible) {
+                for (int i = 0; i < k; ++i) x[P[i]] = z[i];
+                break;
+            }
+            double alpha = 1.0;                                    // step towards z until the first variable hits 0
+            int hit = -1;
+            for (int i = 0; i < k; ++i)
+                if (z[i] <= 0.0) {
+                    const double a = x[P[i]] / (x[P[i]] - z[i]);
+                    if (hit < 0 || a < alpha) { alpha = a; hit = i; }
+                }
+            for (int i = 0; i < k; ++i) x[P[i]] += alpha * (z[i] - x[P[i]]);
+            x[P[hit]] = 0.0;
+            std::vector<int> keep;
+            bool dropped_new = false;
+            for (int i = 0; i < k; ++i) {
+                const int v = P[i];
+                if (x[v] <= 0.0) {
+                    x[v] = 0.0;
+                    passive[v] = 0;
+                    dropped_new = dropped_new || v == t;
+                } else {
+                    keep.push_back(v);
+                }
+            }
+            P.swap(keep);
+            for (int i = 0; i < r; ++i) excluded[i] = 0;           // the passive set changed: dependencies may too
+            if (dropped_new && inner == 0) excluded[t] = 1;        // the newcomer cannot enter: no cycling on it
+        }
+        gradient();
+    }
+}
+
+}  // namespace
+
+extern "C" int grx_host_nnls(int r, int m, const double *GtG, const double *GtM, const double *MtM_diag, double *E)
+{
+    GRX_REQUIRE(r >= 1 && r <= GRX_MAX_ROLES, "grx_host_nnls: r = %d outside [1, %d]", r, GRX_MAX_ROLES);
+    GRX_REQUIRE(m >= 0, "grx_host_nnls: m = %d", m);
+    if (m == 0) return GRX_OK;
+    GRX_REQUIRE(GtG && GtM && E, "grx_host_nnls: null pointer");
+    double max_diag = 0.0;
+    for (int i = 0; i < r; ++i) {
+        GRX_REQUIRE(std::isfinite(GtG[(size_t)i * r + i]) && GtG[(size_t)i * r + i] >= 0.0,
+                    "grx_host_nnls: G^T G has a negative or non-finite diagonal");
+        max_diag = std::max(max_diag, GtG[(size_t)i * r + i]);
+    }
+    std::vector<double> b(r), x(r);
+    for (int j = 0; j < m; ++j) {
+        double bmax = 0.0;
+        for (int i = 0; i < r; ++i) {
+            b[i] = GtM[(size_t)i * m + j];
+            GRX_REQUIRE(std::isfinite(b[i]), "grx_host_nnls: G^T M column %d is not finite", j);
+            bmax = std::max(bmax, std::fabs(b[i]));
+        }
+        // |b_i| <= ||g_i|| ||m_j||: the scale of the gradient
+        const double scale = (MtM_diag && MtM_diag[j] > 0.0) ? std::sqrt(max_diag) * std::sqrt(MtM_diag[j]) : bmax;
+        if (scale > 0.0) nnls_column(r, GtG, b.data(), 1e-13 * scale, x.data());
+        else std::fill(x.begin(), x.end(), 0.0);
+        for (int i = 0; i < r; ++i) E[(size_t)i * m + j] = x[i];
+    }
+    return GRX_OK;
+}

@@ -1136,3 +1136,86 @@ def nmf_fit(X: torch.Tensor, n: int, r: int, omega: np.ndarray, tol: float, max_
     state = NmfState(X, n, W, H, x_sq_norm=float(info.x_sq_norm))
     state.info = info
     return state, int(info.n_iter)
+
+
+# ---------------------------------------------------------------------------------------------- sense making
+def row_counts(csr: DeviceCSR, add_self_loop: bool) -> torch.Tensor:
+    """grx_row_sums with the weights ignored: neighbour counts (networkx G.degree() of a weighted graph)."""
+    out = zeros(csr.n, dtype=torch.float64)
+    _lib.call('grx_row_sums', csr.n, _ptr(csr.row_ptr), _ptr(csr.col), None, int(add_self_loop), 0, csr.n, _ptr(out),
+              _stream())
+    return out
+
+
+def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alpha: float, tol: float,
+           max_iter: int) -> Tuple[torch.Tensor, int]:
+    n = csr_in.n
+    lib = _lib.load()
+    ws_bytes = getattr(lib, name + '_workspace_bytes')(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    x = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    iters = ctypes.c_int(0)
+    graph = (n, _ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.w))
+    hubs = (_ptr(csr_in.hub_rows), csr_in.n_hubs, csr_in.lanes_per_row)
+    if name == 'grx_pagerank':
+        args = graph + (_ptr(out_weight),) + hubs + (float(alpha), float(tol))
+    else:
+        args = graph + hubs + (float(tol),)
+    rc = getattr(lib, name)(*args, int(max_iter), _ptr(x), ctypes.byref(iters), _ptr(ws), ws_bytes, _stream())
+    if rc == -6:
+        raise _lib.ConvergenceError(f'power iteration failed to converge within {max_iter} iterations',
+                                    iterations=iters.value)
+    _lib.check(rc, name)
+    return x, int(iters.value)
+
+
+def pagerank(csr_in: DeviceCSR, out_weight: torch.Tensor, alpha: float, tol: float,
+             max_iter: int) -> Tuple[torch.Tensor, int]:
+    """grx_pagerank over the in-adjacency csr_in; out_weight = out-weight row sums.  (x, iterations)."""
+    return _power('grx_pagerank', csr_in, out_weight, alpha, tol, max_iter)
+
+
+def eigenvector_centrality(csr_in: DeviceCSR, tol: float, max_iter: int) -> Tuple[torch.Tensor, int]:
+    """grx_eigenvector_centrality over the in-adjacency csr_in.  (x, iterations)."""
+    return _power('grx_eigenvector_centrality', csr_in, None, 0.0, tol, max_iter)
+
+
+def local_structure(csr: DeviceCSR, T: torch.Tensor, has_loops: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """grx_local_structure_measures: (clustering, effective_size) of an undirected graph from its triangle counts."""
+    n = csr.n
+    cl = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    es = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    scratch = torch.empty(max(n, 1), dtype=torch.uint8, device=device()) if has_loops else None
+    _lib.call('grx_local_structure_measures', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(T), _ptr(scratch), _ptr(cl),
+              _ptr(es), _stream())
+    return cl, es
+
+
+def sense_normal_equations(G: np.ndarray, M: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """G^T G (r x r), G^T M (r x m) and the squared column norms of M from grx_gram over [G | M_chunk] (feature-major
+    on the device, at most 128 columns per pass)."""
+    n, r = G.shape
+    m = M.shape[1]
+    width = max(128 - r, 1)
+    GtG = None
+    GtM = np.zeros((r, m))
+    mm = np.zeros(m)
+    for c0 in range(0, max(m, 1), width):
+        c1 = min(c0 + width, m)
+        X = to_device(np.ascontiguousarray(np.vstack([G.T, M[:, c0:c1].T]), dtype=np.float64))
+        Gram, _ = gram(X, n)
+        GtG = Gram[:r, :r].copy() if GtG is None else GtG
+        GtM[:, c0:c1] = Gram[:r, r:]
+        mm[c0:c1] = np.diag(Gram)[r:]
+    return GtG, GtM, mm
+
+
+def nnls(GtG: np.ndarray, GtM: np.ndarray, mm: Optional[np.ndarray] = None) -> np.ndarray:
+    """grx_host_nnls (host): E >= 0 minimising ||G E - M||_F from the normal equations."""
+    GtG = np.ascontiguousarray(GtG, dtype=np.float64)
+    GtM = np.ascontiguousarray(GtM, dtype=np.float64)
+    r, m = GtM.shape
+    E = np.zeros((r, m))
+    mm = None if mm is None else np.ascontiguousarray(mm, dtype=np.float64)
+    _lib.call('grx_host_nnls', r, m, _hptr(GtG), _hptr(GtM), _hptr(mm), _hptr(E))
+    return E

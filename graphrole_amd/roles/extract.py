@@ -59,6 +59,7 @@ class RoleExtractor:
 
         self.node_role_factor: Optional[pd.DataFrame] = None
         self.role_feature_factor: Optional[pd.DataFrame] = None
+        self.role_measure_factor: Optional[pd.DataFrame] = None
         self.model_selection_ = None
 
     @property
@@ -125,6 +126,61 @@ class RoleExtractor:
 
     def explain(self):
         raise NotImplementedError('Role explanation ("sense making") is not yet implemented.')
+
+    def sense_making(self, measures: pd.DataFrame, normalize: bool = False) -> pd.DataFrame:
+        """
+        New (RolX sense making, Henderson et al., KDD 2012): the non-negative role x measure table E with
+        node_role_factor @ E ~ measures, column by column min ||G e - m|| over e >= 0.
+
+        :param measures: node x measure table, e.g. ``graphrole_amd.node_measures(G)``, a user-computed column such as
+          betweenness, or the feature table itself; rows are matched to ``node_role_factor.index`` by label (any
+          order, the same label set).  Every entry must be a finite number: fill gaps first, e.g.
+          ``sense_making(measures.fillna(0))``
+        :param normalize: divide every measure by its mean over the nodes first (a measure with mean 0 gives a
+          column of zeros), so that measures of different scales compare across columns
+        :return: DataFrame index role_0 ..., columns = the measures'; also stored as ``role_measure_factor``
+
+        G^T G and G^T M come from one device pass over [G | M] (grx_gram); the NNLS is grx_host_nnls.  A
+        ``distributed`` extractor runs this replicated: every rank holds the same factors.  ``explain()`` is the
+        reference's stub and still raises NotImplementedError: this method is the sense-making entry point.
+        """
+        if self.node_role_factor is None:
+            raise ValueError('sense_making needs fitted roles: call extract_role_factors first')
+        if not isinstance(measures, pd.DataFrame):
+            raise ValueError(f'measures must be a pandas DataFrame (got {type(measures).__name__})')
+        index = self.node_role_factor.index
+        if measures.index.has_duplicates:
+            raise ValueError('measures has duplicate row labels')
+        if len(measures.index) != len(index) or not measures.index.isin(index).all():
+            raise ValueError('measures must have one row per node of node_role_factor (the same labels)')
+        if not measures.index.equals(index):
+            measures = measures.reindex(index)
+        values = np.empty(measures.shape, dtype=np.float64)
+        for j, name in enumerate(measures.columns):
+            column = measures.iloc[:, j]
+            if not (pd.api.types.is_numeric_dtype(column.dtype) or pd.api.types.is_bool_dtype(column.dtype)):
+                raise ValueError(f'measure {name!r} is not numeric (dtype {column.dtype})')
+            col = column.to_numpy(dtype=np.float64, na_value=np.nan)
+            bad = int(np.count_nonzero(~np.isfinite(col)))
+            if bad:
+                raise ValueError(f'measure {name!r} has {bad} non-finite entries (NaN or inf); fill them first, '
+                                 f'e.g. measures.fillna(0)')
+            values[:, j] = col
+        if normalize and values.shape[0]:
+            means = values.mean(axis=0)
+            nonzero = means != 0
+            values[:, nonzero] /= means[nonzero]
+            values[:, ~nonzero] = 0.0
+        from graphrole_amd import backend
+        K = backend.get()
+        G = np.ascontiguousarray(self.node_role_factor.to_numpy(dtype=np.float64))
+        if values.shape[1] == 0:
+            E = np.zeros((G.shape[1], 0))
+        else:
+            GtG, GtM, mm = K.sense_normal_equations(G, values)
+            E = K.nnls(GtG, GtM, mm)
+        self.role_measure_factor = pd.DataFrame(E, index=self.node_role_factor.columns, columns=measures.columns)
+        return self.role_measure_factor
 
     def _plan(self, n_rows: int):
         """Row shards of the feature table (equal row counts: every row of the NMF passes costs the same)."""

@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define GRX_VERSION 600          /* 0.6.0: grx_kmeans1d reports into int32[4] (d_info[3] = consistency faults of the seeding) */
+#define GRX_VERSION 700          /* 0.7.0: node measures of RolX sense making (grx_pagerank, grx_eigenvector_centrality,
+                                    grx_local_structure_measures) and grx_host_nnls; status GRX_ERR_NOT_CONVERGED */
 #define GRX_MAX_BINS 128         /* upper bound on vertical-log bins (n < 2^63 gives < 70) */
 #define GRX_MAX_ROLES 32         /* NMF rank limit of the device kernels: 1 .. 16 fused fp64-MFMA passes; 17 .. 32
                                     a composed update (several times the traffic), then with n_roles + features <= 480 */
@@ -44,7 +45,9 @@ typedef enum {
     GRX_ERR_HIP = -2,            /* HIP runtime error (message has hipGetErrorString) */
     GRX_ERR_WORKSPACE = -3,      /* workspace too small */
     GRX_ERR_UNSUPPORTED = -4,    /* shape outside the compiled limits */
-    GRX_ERR_DEGENERATE = -5      /* numerically degenerate input (e.g. an all-zero feature matrix) */
+    GRX_ERR_DEGENERATE = -5,     /* numerically degenerate input (e.g. an all-zero feature matrix) */
+    GRX_ERR_NOT_CONVERGED = -6   /* a power iteration did not meet its tolerance within max_iter iterations (the
+                                    iteration count is still written; networkx raises PowerIterationFailedConvergence) */
 } grx_status;
 
 /* Environment switches, each read once per process; all of them select between formulations that the tests compare
@@ -763,6 +766,56 @@ int grx_transpose(int64_t rows, int64_t cols, const double *d_in, int64_t ld_in,
  */
 int grx_role_argmax(int64_t n, int r, const double *d_G, int32_t *d_first_max, void *stream);
 int grx_row_normalise(int64_t n, int r, const double *d_G, double *d_share, void *stream);
+
+/* ------------------------------------------------------------------ sense making -------- */
+/*
+ * Node measures of RolX sense making (Henderson et al., KDD 2012: E >= 0 with G E ~ M, M = node x measure table).
+ * The reference's RoleExtractor.explain() is a stub (graphrole/roles/extract.py); each measure restates networkx 3.4.2.
+ * Graph arguments are the CSR convention above; every vector is in the caller's row order.
+ *
+ * grx_pagerank restates networkx.pagerank(G, alpha, weight='weight', tol, max_iter) (pagerank_alg.py,
+ *   _pagerank_scipy): x0 = 1/N, x' = alpha (x A + sum(x[dangling]) / N) + (1 - alpha) / N with A = W scaled by the
+ *   inverse out-weight, dangling = out-weight 0; stop at the first iteration with sum |x' - x| < N tol.
+ *   d_in_*: the IN-adjacency, pulled (undirected: the CSR itself; directed: the transposed CSR), d_in_w NULL = 1.
+ *   d_out_weight: fp64[n] out-weight row sums of the same graph (an undirected self-loop once).
+ * grx_eigenvector_centrality restates networkx.eigenvector_centrality(G, max_iter, tol, weight='weight')
+ *   (eigenvector.py): x0 = 1/N, x' = (A^T + I) x normalised to unit L2 norm, same stopping rule.
+ * Both: rows longer than GRX_HUB_FACTOR * lanes_per_row (4, 8, 16 or 32 lanes per row) must be listed in
+ *   d_hub_rows (int32 row ids) and are summed by a workgroup each.  The iterations are enqueued in batches; a device
+ *   `done` word makes the launches after convergence return at once, the host reads it back once per batch.
+ *   *h_iterations = iterations run.  Returns GRX_ERR_NOT_CONVERGED (d_x untouched) when max_iter iterations did not
+ *   converge.  Deterministic: no floating-point atomics, partial sums reduced in a fixed order.
+ *   d_workspace: grx_*_workspace_bytes(n) bytes.
+ */
+size_t grx_pagerank_workspace_bytes(int64_t n);
+int grx_pagerank(int64_t n, const int64_t *d_in_row_ptr, const int32_t *d_in_col, const double *d_in_w,
+                 const double *d_out_weight, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                 double alpha, double tol, int max_iter, double *d_x, int *h_iterations, void *d_workspace,
+                 size_t workspace_bytes, void *stream);
+size_t grx_eigenvector_centrality_workspace_bytes(int64_t n);
+int grx_eigenvector_centrality(int64_t n, const int64_t *d_in_row_ptr, const int32_t *d_in_col, const double *d_in_w,
+                               const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row, double tol,
+                               int max_iter, double *d_x, int *h_iterations, void *d_workspace, size_t workspace_bytes,
+                               void *stream);
+/*
+ * grx_local_structure_measures restates, for an undirected graph without parallel edges, networkx.clustering(G)
+ *   (cluster.py, _triangles_and_degree_iter: 0 if T = 0 else 2T / (d' (d' - 1))) and networkx.effective_size(G)
+ *   (structuralholes.py, Borgatti: d' - 2t / d', t = T + number of neighbours with a self-loop; NaN for an isolated
+ *   node).  d' = degree without the self-loop, T = per-node triangle counts of grx_triangle_counts.  The same IEEE
+ *   operations in the same order: bit-equal.  One divergence: a node whose only neighbour is itself gets NaN
+ *   (networkx raises ZeroDivisionError).  d_loop_scratch: uint8[n] when the graph has self-loops, NULL when it has
+ *   none (then d_col is not read).
+ */
+int grx_local_structure_measures(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const uint64_t *d_T,
+                                 uint8_t *d_loop_scratch, double *d_clustering, double *d_effective_size, void *stream);
+/*
+ * grx_host_nnls: HOST.  Column by column, min_{e >= 0} || G e - m_j ||^2 from the normal equations (h_GtG r x r,
+ *   h_GtM r x m, both row-major, from one grx_gram pass over [G | M]); Lawson-Hanson active set with a Cholesky
+ *   factorisation of the passive block (scipy.optimize.nnls solves the same problem from G and M themselves).
+ *   r <= GRX_MAX_ROLES, any m.  h_MtM_diag (optional, m values ||m_j||^2) scales the optimality tolerance.  Roles that
+ *   are all zero, or linearly dependent on roles already passive, stay at 0.  h_E: r x m row-major.
+ */
+int grx_host_nnls(int r, int m, const double *h_GtG, const double *h_GtM, const double *h_MtM_diag, double *h_E);
 
 #ifdef __cplusplus
 }
