@@ -13,7 +13,7 @@ def __getattr__(name):
     if name == 'RoleExtractor':
         from .roles.extract import RoleExtractor
         return RoleExtractor
-    if name in ('node_measures', 'ConvergenceError'):
+    if name in ('node_measures', 'betweenness_centrality', 'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     raise AttributeError(name)

@@ -244,6 +244,10 @@ _SIGNATURES = {
     'grx_local_structure_measures': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
     'grx_host_nnls': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'grx_betweenness_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
+    'grx_betweenness': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                c_int64, c_int, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -103,6 +103,13 @@ class DeviceGraphInterface(BaseGraphInterface):
             self._has_loops = getattr(g, 'n_loops', 1) > 0
         return self._dev
 
+    def _structure_csrs(self):
+        """(out CSR, in CSR or None for an undirected graph) of the graph's DISTINCT arcs in internal order -- the
+        adjacency a BFS over ``G[v]`` walks (betweenness).  Here the device graph itself: parallel edges are merged
+        into one arc by ``to_csr()``."""
+        _, out, tr = self._device_graph()
+        return out, tr
+
     #: False forces the host-side construction (InternalGraph + upload); tests compare the two
     _device_ingest = True
     #: set by _device_graph; True = look the diagonal up (always right, slower)

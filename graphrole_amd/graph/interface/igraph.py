@@ -153,6 +153,18 @@ class IgraphInterface(DeviceGraphInterface):
             self._dev = (host, agg, None)
         return self._dev
 
+    def _structure_csrs(self):
+        """With loops / parallel edges the device graph is the neighbour multiset (one column per parallel edge, no
+        transposed CSR): the distinct arcs are the edge_weights dict graph instead, and its transpose."""
+        if self._is_simple():
+            return super()._structure_csrs()
+        host = self._device_graph()[0]
+        if not self.directed:
+            return self._struct, None
+        if getattr(self, '_struct_in', None) is None:
+            self._struct_in = self._K().DeviceCSR(host.t_row_ptr, host.t_col, host.t_w)
+        return self._struct, self._struct_in
+
     def local_feature_columns(self):
         if self._is_simple():
             return super().local_feature_columns()

@@ -1219,3 +1219,24 @@ def nnls(GtG: np.ndarray, GtM: np.ndarray, mm: Optional[np.ndarray] = None) -> n
     mm = None if mm is None else np.ascontiguousarray(mm, dtype=np.float64)
     _lib.call('grx_host_nnls', r, m, _hptr(GtG), _hptr(GtM), _hptr(mm), _hptr(E))
     return E
+
+
+def betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.ndarray, endpoints: bool, scale: float,
+                batch: int = 0) -> torch.Tensor:
+    """grx_betweenness: unweighted Brandes from `sources` (internal row ids, in accumulation order) over the
+    out-adjacency csr_out and the in-adjacency csr_in (None for an undirected graph); bc multiplied by `scale`.
+    batch = sources per batch (a multiple of 64; 0 = the library's choice)."""
+    n = csr_out.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    lib = _lib.load()
+    ws_bytes = lib.grx_betweenness_workspace_bytes(n, int(batch), len(src))   # sized for the B the call uses
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    bc = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    if csr_in is None:
+        in_args = (None, None, None, 0, 0)
+    else:
+        in_args = (_ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.hub_rows), csr_in.n_hubs, csr_in.lanes_per_row)
+    _lib.call('grx_betweenness', n, _ptr(csr_out.row_ptr), _ptr(csr_out.col), _ptr(csr_out.hub_rows), csr_out.n_hubs,
+              csr_out.lanes_per_row, *in_args, _ptr(src), len(src), int(bool(endpoints)), float(scale), int(batch),
+              _ptr(bc), _ptr(ws), ws_bytes, _stream())
+    return bc

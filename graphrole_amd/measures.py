@@ -4,10 +4,13 @@ Node measures for RolX sense making (Henderson et al., KDD 2012, section 4): the
 default arguments and is computed on the device CSR the feature extractor uses (graph/interface/base.py
 ``_device_graph``): degrees by grx_row_sums, clustering and effective size by grx_local_structure_measures on the
 triangle counts of grx_triangle_counts, PageRank and eigenvector centrality by the power iterations of
-csrc/grx_measures.hip.
+csrc/grx_measures.hip, and betweenness centrality (opt-in: O(n m)) by the batched Brandes passes of
+csrc/grx_betweenness.hip.
 """
 from __future__ import annotations
 
+import random
+from numbers import Integral
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -25,7 +28,12 @@ CATALOGUE = {
     'effective_size': 'nx.effective_size(G)',
     'pagerank': "nx.pagerank(G, alpha, weight='weight', tol=tol, max_iter=max_iter)",
     'eigenvector': "nx.eigenvector_centrality(G, max_iter=max_iter, tol=tol, weight='weight')",
+    'betweenness_centrality': 'nx.betweenness_centrality(G, k=k, normalized=normalized, endpoints=endpoints, '
+                              'seed=seed)',
 }
+
+#: catalogue entries computed only when named: not in ``available_measures`` nor in the default table
+OPT_IN = ('betweenness_centrality',)
 
 
 def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
@@ -45,8 +53,8 @@ def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
 
 
 def available_measures(directed: bool, multi: bool) -> List[str]:
-    """The catalogue entries defined for a graph of this kind, in catalogue order."""
-    return [name for name in CATALOGUE if _unavailable(name, directed, multi) is None]
+    """The catalogue entries defined for a graph of this kind, in catalogue order (the opt-in ones excepted)."""
+    return [name for name in CATALOGUE if name not in OPT_IN and _unavailable(name, directed, multi) is None]
 
 
 def _adapter(G):
@@ -74,15 +82,18 @@ def _count_csrs(graph, K, host):
 
 
 def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
-                  max_iter: int = 100) -> pd.DataFrame:
+                  max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
+                  endpoints: bool = False) -> pd.DataFrame:
     """
     Node x measure table of well-known graph measures, computed on the GPU.
 
     :param G: any graph ``RecursiveFeatureExtractor`` accepts (networkx graph or multigraph, CSRGraph, igraph)
     :param measures: names from ``CATALOGUE`` in the order of the columns; None = every measure defined for the
-      graph's kind (``available_measures``)
+      graph's kind (``available_measures``; ``OPT_IN`` measures such as ``'betweenness_centrality'`` only when named)
     :param alpha, tol, max_iter: networkx's arguments of pagerank (alpha, tol, max_iter) and eigenvector_centrality
       (tol, max_iter)
+    :param k, seed, normalized, endpoints: networkx's arguments of betweenness_centrality (see
+      ``betweenness_centrality``); they apply to ``'betweenness_centrality'`` only
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
     :raises ValueError: an unknown measure name
@@ -93,11 +104,13 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     Stated divergence: ``effective_size`` of a node whose only neighbour is itself is NaN (networkx raises
     ZeroDivisionError).
     """
-    return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter)
+    return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter, k=k, seed=seed,
+                       normalized=normalized, endpoints=endpoints)
 
 
 def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
-                max_iter: int = 100) -> pd.DataFrame:
+                max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
+                endpoints: bool = False) -> pd.DataFrame:
     """``node_measures`` on an existing graph adapter (its device CSR is built once and reused)."""
     directed = bool(graph.directed)
     multi = bool(getattr(graph, '_multi', False))
@@ -112,6 +125,8 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             why = _unavailable(nm, directed, multi)
             if why is not None:
                 raise NotImplementedError(why)
+    if 'betweenness_centrality' in names:
+        sources = _betweenness_sources(graph, k, seed)        # argument errors before any device work
     K = graph._K()
     host, out, tr = graph._device_graph()
     loops = bool(graph._has_loops)
@@ -148,6 +163,15 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col, dt = local()[0], np.dtype('float64')
         elif nm == 'effective_size':
             col, dt = local()[1], np.dtype('float64')
+        elif nm == 'betweenness_centrality':
+            # BFS walks G[v]: the distinct arcs, out and (directed) in, not a neighbour multiset
+            s_out, s_in = graph._structure_csrs()
+            if directed and s_in is None:
+                raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; '
+                                          f'betweenness_centrality cannot be computed on it')
+            col = K.betweenness(s_out, s_in if directed else None, np.asarray(host.inv)[sources], endpoints,
+                                _rescale_factor(host.n, normalized, directed, k, endpoints))
+            dt = np.dtype('float64')
         elif nm == 'pagerank':
             col, iterations[nm] = K.pagerank(tr if directed else out, K.row_sums(out, False), alpha, tol, max_iter)
             dt = np.dtype('float64')
@@ -159,3 +183,75 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
     frame = graph._frame(names, cols, dtypes)
     frame.attrs['iterations'] = iterations
     return frame
+
+
+def _py_random_state(seed) -> random.Random:
+    """networkx's @py_random_state for int, None and random.Random seeds (None = the global state of `random`)."""
+    if seed is None:
+        return random._inst
+    if isinstance(seed, random.Random):
+        return seed
+    if isinstance(seed, Integral):
+        return random.Random(seed)
+    raise TypeError(f'seed must be an int, None or a random.Random instance (got {type(seed).__name__}); '
+                    f'networkx also accepts numpy random states, this implementation does not')
+
+
+def _betweenness_sources(graph, k: Optional[int], seed) -> np.ndarray:
+    """networkx's source list -- every node in the graph's own order, or seed.sample(list(G), k) -- as rows of
+    ``graph.to_csr()`` (sorted labels), in that order."""
+    nodes = list(graph.get_nodes())
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, Integral) or not 1 <= k <= len(nodes):
+            raise ValueError(f'k must be an integer in 1..{len(nodes)} (the number of nodes), got {k!r}')
+        nodes = _py_random_state(seed).sample(nodes, int(k))
+    labels = graph.to_csr().labels
+    if isinstance(labels, range) and labels == range(len(labels)):
+        return np.asarray(nodes, dtype=np.int64)
+    row_of = {label: i for i, label in enumerate(labels)}
+    return np.fromiter((row_of[v] for v in nodes), dtype=np.int64, count=len(nodes))
+
+
+def _rescale_factor(n: int, normalized: bool, directed: bool, k: Optional[int], endpoints: bool) -> float:
+    """The factor of networkx's _rescale (1.0 where networkx leaves the sums as they are)."""
+    if normalized:
+        if endpoints:
+            scale = None if n < 2 else 1 / (n * (n - 1))
+        elif n <= 2:
+            scale = None
+        else:
+            scale = 1 / ((n - 1) * (n - 2))
+    else:
+        scale = None if directed else 0.5
+    if scale is not None and k is not None:
+        scale = scale * n / k
+    return 1.0 if scale is None else scale
+
+
+def betweenness_centrality(G, k: Optional[int] = None, normalized: bool = True, weight=None, endpoints: bool = False,
+                           seed=None) -> pd.Series:
+    """
+    Betweenness centrality on the GPU: networkx 3.4.2's ``betweenness_centrality(G, k, normalized, weight=None,
+    endpoints, seed)`` (Brandes' algorithm, one BFS per source) restated by csrc/grx_betweenness.hip, many sources
+    per batch.
+
+    :param G: any graph ``node_measures`` accepts; multigraph edges count once, self-loops never lie on a shortest path
+    :param k: None = every node is a source, in the graph's own node order (``list(G)``, igraph vertex order, CSRGraph
+      row order); otherwise ``seed.sample(list(nodes), k)`` sources in the sampled order, and the sums scaled by n / k
+    :param normalized, endpoints: as networkx
+    :param weight: must be None (weighted betweenness is Dijkstra's algorithm, not implemented here)
+    :param seed: int (``random.Random(seed)``), None (the global state of ``random``, as networkx) or ``random.Random``
+    :return: float64 Series indexed by the sorted node labels (the index of ``node_measures``)
+    :raises NotImplementedError: weight is not None
+    :raises ValueError: k outside 1..n
+    :raises TypeError: a seed of another type
+
+    Values agree with networkx to 1e-12 relative: only the order of the additions inside one source's dependency
+    delta(v) differs.  Stated divergences: k = 0 raises ValueError (networkx: ZeroDivisionError); a numpy random state
+    as seed raises TypeError (networkx accepts it).
+    """
+    if weight is not None:
+        raise NotImplementedError(f'weighted betweenness (nx.betweenness_centrality(G, weight={weight!r})) is '
+                                  f'Dijkstra-based and not implemented here; use networkx')
+    frame = node_measures(G, ['betweenness_centrality'], k=k, seed=seed, normalized=normalized, endpoints=endpoints)
+    return frame['betweenness_centrality']

@@ -132,8 +132,9 @@ class RoleExtractor:
         New (RolX sense making, Henderson et al., KDD 2012): the non-negative role x measure table E with
         node_role_factor @ E ~ measures, column by column min ||G e - m|| over e >= 0.
 
-        :param measures: node x measure table, e.g. ``graphrole_amd.node_measures(G)``, a user-computed column such as
-          betweenness, or the feature table itself; rows are matched to ``node_role_factor.index`` by label (any
+        :param measures: node x measure table, e.g. ``graphrole_amd.node_measures(G)`` (with
+          ``'betweenness_centrality'`` named, or ``graphrole_amd.betweenness_centrality(G)`` added as a column), a
+          user-computed column, or the feature table itself; rows are matched to ``node_role_factor.index`` by label (any
           order, the same label set).  Every entry must be a finite number: fill gaps first, e.g.
           ``sense_making(measures.fillna(0))``
         :param normalize: divide every measure by its mean over the nodes first (a measure with mean 0 gives a

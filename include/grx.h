@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define GRX_VERSION 700          /* 0.7.0: node measures of RolX sense making (grx_pagerank, grx_eigenvector_centrality,
+#define GRX_VERSION 800          /* 0.8.0: grx_betweenness (unweighted betweenness centrality of the sense-making measures)
+                                    0.7.0: node measures of RolX sense making (grx_pagerank, grx_eigenvector_centrality,
                                     grx_local_structure_measures) and grx_host_nnls; status GRX_ERR_NOT_CONVERGED */
 #define GRX_MAX_BINS 128         /* upper bound on vertical-log bins (n < 2^63 gives < 70) */
 #define GRX_MAX_ROLES 32         /* NMF rank limit of the device kernels: 1 .. 16 fused fp64-MFMA passes; 17 .. 32
@@ -816,6 +817,32 @@ int grx_local_structure_measures(int64_t n, const int64_t *d_row_ptr, const int3
  *   are all zero, or linearly dependent on roles already passive, stay at 0.  h_E: r x m row-major.
  */
 int grx_host_nnls(int r, int m, const double *h_GtG, const double *h_GtM, const double *h_MtM_diag, double *h_E);
+/*
+ * grx_betweenness restates networkx.betweenness_centrality(G, k, normalized, weight=None, endpoints, seed) (betweenness.py,
+ *   unweighted: _single_source_shortest_path_basic, _accumulate_basic / _accumulate_endpoints, _rescale) for the
+ *   sources d_sources[0 .. n_sources) (int32 row ids, distinct or not) in that order -- networkx's `for s in nodes`.
+ *   Per source: a BFS counts the shortest paths sigma (pulled over the in-adjacency, level by level), then deepest
+ *   level first delta(v) = sum over successors w one level deeper of sigma(v) * coeff(w), coeff(w) = (1 + delta(w)) /
+ *   sigma(w) (pulled over the out-adjacency); bc[w] += delta(w) for every reached w != s (endpoints: += delta(w) + 1,
+ *   and bc[s] += reached - 1).  Finally bc *= scale (the caller computes _rescale's factor, 1 for none).
+ *   d_row_ptr / d_col: the out-adjacency; d_in_row_ptr / d_in_col: the in-adjacency (transposed CSR) of a directed
+ *   graph, NULL for an undirected one.  Weights are not read; self-loops never lie on a shortest path.  Rows longer
+ *   than GRX_HUB_FACTOR * lanes_per_row (resp. in_lanes_per_row) must be listed in d_hub_rows (resp. d_in_hub_rows).
+ *   batch: sources per batch B, a multiple of 64 up to 256; 0 = the library's choice: the widest B whose state fits
+ *   4 GiB, but never below 64 (so above ~3.35 M nodes the state is 20 n 64 bytes, more than 4 GiB), and no wider than
+ *   the source list rounded up to 64.  State: 20 n B bytes (level int32, sigma and delta fp64 per node and source).
+ *   Bound: sigma must stay below 2^53 (path counts; networkx's floats round beyond that too).
+ *   Deterministic and the same bits for every B: bc[v] adds its sources' terms one source after another in the order
+ *   of d_sources, no floating-point atomics.  Against networkx only the order of the additions inside one delta(v)
+ *   differs (networkx: reverse BFS order of the successors; here: column order), so results agree to 1e-12 relative.
+ *   d_bc: fp64[n], overwritten.  d_workspace: grx_betweenness_workspace_bytes(n, batch, n_sources) bytes.
+ */
+size_t grx_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources);
+int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                    int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+                    const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
+                    const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch, double *d_bc,
+                    void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
