@@ -13,7 +13,8 @@ def __getattr__(name):
     if name == 'RoleExtractor':
         from .roles.extract import RoleExtractor
         return RoleExtractor
-    if name in ('node_measures', 'betweenness_centrality', 'ConvergenceError'):
+    if name in ('node_measures', 'betweenness_centrality', 'closeness_centrality', 'harmonic_centrality',
+                'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     raise AttributeError(name)

@@ -1,0 +1,405 @@
+// grx_closeness.hip -- per-target BFS distance sums for RolX sense making: the reach counts and distance sums behind
+// networkx 3.4.2's closeness_centrality (closeness.py:107-137) and the reciprocal-distance sums of
+// harmonic_centrality (harmonic.py:68-89), all sources at once by a bitset multi-source BFS (MS-BFS: Then et al.,
+// "The More the Merrier: Efficient Multi-Source Graph Traversal", VLDB 2014).
+//
+// A batch holds S = 64 W sources.  Source lane b of the batch is bit b % 64 of word b / 64; every node holds three
+// masks of W uint64 words, node-major (word w of node v at v * W + w): visited, and the frontier of this level and of
+// the next (two buffers that swap roles every level).  W lanes of a wavefront handle one node, lane w its word w, so
+// reading a neighbour's frontier is one contiguous 8 W-byte load.
+//
+// Level l -> l + 1 pulls over the adjacency it is given: next(v) = (OR over the listed neighbours u of frontier(u)) &
+// active & ~visited(v).  A lane stops scanning once its word of visited(v) | next(v) covers every active source bit
+// (early exit); a node whose visited words are full reads nothing.  Rows longer than GRX_HUB_FACTOR * lanes_per_row
+// are the CSR's hub list and get a workgroup each: its 256 / W lane groups take every (256 / W)-th arc and OR their
+// masks in a tree through LDS.  The node's own writer (lane 0 of its group) then adds, with c = popcount(next(v)) and
+// d = l + 1:
+//   reach(v) += c,  dsum(v) += d c  (int64, exact: dsum <= n^2 < 2^62),
+//   harm(v)  += c q(d), q(d) = fl(1 / d) 2^84 as an unsigned 128-bit integer: for d < 2^31 the fp64 value fl(1 / d)
+//              is a whole multiple of 2^-84, and the sum stays below n_sources 2^84 < 2^115.
+// A one-thread finalize advances the device level or sets `done` when a level reached nothing new; every launch
+// returns at once after `done`, so the host enqueues levels in batches and reads (done, level) back once per
+// batch.  At the end harmonic(v) = harm(v) 2^-84, rounded once to nearest-even: the correctly rounded sum of the fp64
+// terms fl(1 / d), the same bits for every W, source order and run.  Integer arithmetic only; no floating-point
+// atomics (the source bits are set with integer atomicOr).
+#pragma clang fp contract(off)
+
+#include "grx_common.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int CL_BLOCK = 256;
+constexpr int CL_MAX_WORDS = 16;
+constexpr int CL_LEVEL_BATCH = 8;                            // levels enqueued between two read-backs
+constexpr int CL_MAX_ROW_BLOCKS = 8192;
+constexpr size_t CL_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of W
+constexpr int CL_HARM_SHIFT = 84;                            // harm(v) holds sum c fl(1 / d) scaled by 2^84
+
+enum { CT_DONE = 0, CT_LEVEL, CT_FOUND, CT_COUNT };
+
+bool valid_words(int w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; }
+
+// W of words = 0: the narrowest power of two that holds the source list, but no wider than the widest power of two
+// up to 16 whose state (visited + two frontiers, 24 n bytes per word) fits CL_DEFAULT_STATE_BYTES, and at least 1
+int choose_words(int64_t n, int words, int64_t n_sources)
+{
+    if (words > 0) return words;
+    const size_t per_word = (size_t)(n > 0 ? n : 1) * 24;
+    int widest = 1;
+    while (widest < CL_MAX_WORDS && per_word * (size_t)(widest * 2) <= CL_DEFAULT_STATE_BYTES) widest *= 2;
+    const int64_t needed = grx_ceil_div(std::max<int64_t>(n_sources, 1), GRX_WAVE);
+    int w = 1;
+    while (w < widest && w < needed) w *= 2;
+    return w;
+}
+
+size_t ws_bytes(int64_t n, int W)
+{
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    return 3 * grx_align_up(nn * (size_t)W * 8, 256) + grx_align_up(nn * 16, 256) + 256;
+}
+
+struct ClWs {
+    uint64_t *visited, *f0, *f1;
+    uint64_t *harm;                                          // (lo, hi) per node
+    int32_t *ctrl;
+};
+
+ClWs carve(void *base, int64_t n, int W)
+{
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    char *p = reinterpret_cast<char *>(base);
+    ClWs ws;
+    ws.visited = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
+    ws.f0 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
+    ws.f1 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
+    ws.harm = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * 16, 256);
+    ws.ctrl = reinterpret_cast<int32_t *>(p);
+    return ws;
+}
+
+// the source bits of word w that belong to the batch's `count` sources
+__device__ __forceinline__ uint64_t active_mask(int count, int w)
+{
+    const int bits = count - w * GRX_WAVE;
+    return bits >= GRX_WAVE ? ~0ull : bits <= 0 ? 0ull : (1ull << bits) - 1;
+}
+
+// sum over the W lanes of a group (every lane of the wavefront takes part)
+template <int W>
+__device__ __forceinline__ int group_sum(int c)
+{
+#pragma unroll
+    for (int off = 1; off < W; off <<= 1) c += __shfl_xor(c, off, W);
+    return c;
+}
+
+// OR of word w of frontier(u) over the arcs [b, e) with stride `step`, masked to `want`; stops once `want` is covered
+template <int W>
+__device__ __forceinline__ uint64_t pull_words(int64_t b, int64_t e, int step, const int32_t *__restrict__ col,
+                                               const uint64_t *__restrict__ F, int w, uint64_t want)
+{
+    if (!want) return 0;
+    uint64_t acc = 0;
+    int64_t j = b;
+    for (; j + 3 * step < e; j += 4 * step) {
+        const int64_t u0 = col[j], u1 = col[j + step], u2 = col[j + 2 * step], u3 = col[j + 3 * step];
+        acc |= (F[u0 * W + w] | F[u1 * W + w]) | (F[u2 * W + w] | F[u3 * W + w]);
+        if ((acc & want) == want) return want;
+    }
+    for (; j < e; j += step) {
+        acc |= F[(int64_t)col[j] * W + w];
+        if ((acc & want) == want) return want;
+    }
+    return acc & want;
+}
+
+// the node's writer: c newly reached sources at distance d
+__device__ __forceinline__ void add_level(int64_t v, int c, int d, int64_t *__restrict__ reach,
+                                          int64_t *__restrict__ dsum, uint64_t *__restrict__ harm)
+{
+    reach[v] += c;
+    dsum[v] += (int64_t)d * c;
+    // fl(1 / d) = m 2^(e - 52) with a 53-bit m and -31 <= e <= 0 (1 <= d < 2^31): times 2^84 is m << (e + 32)
+    const double r = 1.0 / (double)d;
+    const uint64_t bits = (uint64_t)__double_as_longlong(r);
+    const int e = (int)((bits >> 52) & 0x7ff) - 1023;
+    const uint64_t m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
+    const unsigned __int128 q = (unsigned __int128)m << (e + 32);
+    unsigned __int128 h = ((unsigned __int128)harm[2 * v + 1] << 64) | harm[2 * v];
+    h += (unsigned __int128)(uint64_t)c * q;
+    harm[2 * v] = (uint64_t)h;
+    harm[2 * v + 1] = (uint64_t)(h >> 64);
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void cl_zero_kernel(int64_t words, uint64_t *__restrict__ a)
+{
+    for (int64_t i = (int64_t)blockIdx.x * CL_BLOCK + threadIdx.x; i < words; i += (int64_t)gridDim.x * CL_BLOCK)
+        a[i] = 0;
+}
+
+// lane b < count: bit b of source s_b's visited and frontier words (integer atomics: one node may be the source of
+// several lanes of a word); level 0
+__global__ __launch_bounds__(CL_BLOCK) void cl_source_init_kernel(int64_t n, int W, int count,
+                                                                  const int32_t *__restrict__ src,
+                                                                  uint64_t *__restrict__ visited,
+                                                                  uint64_t *__restrict__ f0,
+                                                                  int32_t *__restrict__ ctrl)
+{
+    for (int b = blockIdx.x * CL_BLOCK + threadIdx.x; b < count; b += gridDim.x * CL_BLOCK) {
+        const int64_t s = src[b];
+        if (s < 0 || s >= n) continue;                      // an id outside [0, n) is never written through
+        const int64_t cell = s * W + b / GRX_WAVE;
+        const unsigned long long bit = 1ull << (b % GRX_WAVE);
+        atomicOr(reinterpret_cast<unsigned long long *>(&visited[cell]), bit);
+        atomicOr(reinterpret_cast<unsigned long long *>(&f0[cell]), bit);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl[CT_DONE] = 0; ctrl[CT_LEVEL] = 0; ctrl[CT_FOUND] = 0; }
+}
+
+// one level, rows up to hub_degree arcs: W lanes per node, CL_BLOCK / W nodes per workgroup and grid step
+template <int W>
+__global__ __launch_bounds__(CL_BLOCK) void cl_level_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+                                                            const int32_t *__restrict__ col, int64_t hub_degree,
+                                                            int count, uint64_t *__restrict__ visited,
+                                                            uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
+                                                            int64_t *__restrict__ reach, int64_t *__restrict__ dsum,
+                                                            uint64_t *__restrict__ harm, int32_t *__restrict__ ctrl)
+{
+    constexpr int GROUPS = CL_BLOCK / W;
+    if (ctrl[CT_DONE]) return;
+    const int l = ctrl[CT_LEVEL];
+    const uint64_t *F = (l & 1) ? f1 : f0;
+    uint64_t *Fn = (l & 1) ? f0 : f1;
+    const int w = threadIdx.x % W;
+    const uint64_t active = active_mask(count, w);
+    int found = 0;
+    // the trip count is the same in every lane of the workgroup: the group sums below see every lane
+    for (int64_t first = (int64_t)blockIdx.x * GROUPS; first < n; first += (int64_t)gridDim.x * GROUPS) {
+        const int64_t v = first + threadIdx.x / W;
+        bool mine = false;
+        int c = 0;
+        if (v < n) {
+            const int64_t b = row_ptr[v], e = row_ptr[v + 1];
+            if (e - b <= hub_degree) {                      // longer rows: cl_level_hub_kernel
+                mine = true;
+                const int64_t cell = v * W + w;
+                const uint64_t vw = visited[cell];
+                const uint64_t nw = pull_words<W>(b, e, 1, col, F, w, active & ~vw);
+                Fn[cell] = nw;
+                if (nw) visited[cell] = vw | nw;
+                c = __popcll(nw);
+            }
+        }
+        c = group_sum<W>(c);
+        if (mine && w == 0 && c) {
+            add_level(v, c, l + 1, reach, dsum, harm);
+            found = 1;
+        }
+    }
+    if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[CT_FOUND] = 1;
+}
+
+// one level, hub rows: one workgroup per hub row; CL_BLOCK / W lane groups take every (CL_BLOCK / W)-th arc
+template <int W>
+__global__ __launch_bounds__(CL_BLOCK) void cl_level_hub_kernel(const int64_t *__restrict__ row_ptr,
+                                                                const int32_t *__restrict__ col,
+                                                                const int32_t *__restrict__ hub_rows, int count,
+                                                                uint64_t *__restrict__ visited,
+                                                                uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
+                                                                int64_t *__restrict__ reach,
+                                                                int64_t *__restrict__ dsum,
+                                                                uint64_t *__restrict__ harm,
+                                                                int32_t *__restrict__ ctrl)
+{
+    constexpr int GROUPS = CL_BLOCK / W;
+    __shared__ uint64_t part[CL_BLOCK];
+    if (ctrl[CT_DONE]) return;
+    const int l = ctrl[CT_LEVEL];
+    const uint64_t *F = (l & 1) ? f1 : f0;
+    uint64_t *Fn = (l & 1) ? f0 : f1;
+    const int t = threadIdx.x, w = t % W;
+    const int64_t v = hub_rows[blockIdx.x];
+    const int64_t cell = v * W + w;
+    const uint64_t vw = visited[cell];
+    part[t] = pull_words<W>(row_ptr[v] + t / W, row_ptr[v + 1], GROUPS, col, F, w, active_mask(count, w) & ~vw);
+    __syncthreads();
+#pragma unroll
+    for (int s = CL_BLOCK / 2; s >= W; s >>= 1) {          // part[t] for t < W: the OR over every group
+        if (t < s) part[t] |= part[t + s];
+        __syncthreads();
+    }
+    if (t >= GRX_WAVE) return;
+    const uint64_t nw = t < W ? part[t] : 0;
+    const int c = group_sum<W>(__popcll(nw));
+    if (t < W) {
+        Fn[cell] = nw;
+        if (nw) visited[cell] = vw | nw;
+    }
+    if (t == 0 && c) {
+        add_level(v, c, l + 1, reach, dsum, harm);
+        ctrl[CT_FOUND] = 1;
+    }
+}
+
+// one thread: next level, or done when this level reached nothing new
+__global__ void cl_finalize_kernel(int32_t *__restrict__ ctrl)
+{
+    if (ctrl[CT_DONE]) return;
+    if (ctrl[CT_FOUND]) {
+        ctrl[CT_LEVEL] += 1;
+        ctrl[CT_FOUND] = 0;
+    } else {
+        ctrl[CT_DONE] = 1;
+    }
+}
+
+// harmonic(v) = harm(v) 2^-84, rounded once to nearest-even (by hand: the top 53 bits plus the rounding bits below)
+__global__ __launch_bounds__(CL_BLOCK) void cl_harmonic_kernel(int64_t n, const uint64_t *__restrict__ harm,
+                                                               double *__restrict__ out)
+{
+    for (int64_t v = (int64_t)blockIdx.x * CL_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * CL_BLOCK) {
+        const unsigned __int128 h = ((unsigned __int128)harm[2 * v + 1] << 64) | harm[2 * v];
+        double r = 0.0;
+        if (h) {
+            const uint64_t hi = (uint64_t)(h >> 64), lo = (uint64_t)h;
+            const int top = hi ? 128 - __clzll((long long)hi) : 64 - __clzll((long long)lo);   // bit length
+            int shift = top > 53 ? top - 53 : 0;
+            uint64_t m = (uint64_t)(h >> shift);
+            if (shift) {
+                const unsigned __int128 rem = h & (((unsigned __int128)1 << shift) - 1);
+                const unsigned __int128 half = (unsigned __int128)1 << (shift - 1);
+                if (rem > half || (rem == half && (m & 1))) ++m;
+                if (m >> 53) { m >>= 1; ++shift; }
+            }
+            r = ldexp((double)m, shift - CL_HARM_SHIFT);    // m < 2^53 and the power of two: both exact
+        }
+        out[v] = r;
+    }
+}
+
+struct PinnedCtrl {
+    int32_t *h = nullptr;
+    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
+};
+thread_local PinnedCtrl g_ctrl;
+
+int read_ctrl(const int32_t *d_ctrl, int32_t out[2], hipStream_t st)
+{
+    if (!g_ctrl.h) {
+        void *h = nullptr;
+        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
+        g_ctrl.h = reinterpret_cast<int32_t *>(h);
+    }
+    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, 8, st);
+    if (rc == GRX_OK) rc = grx_fetch_wait(st);
+    if (rc != GRX_OK) return rc;
+    out[0] = g_ctrl.h[CT_DONE];
+    out[1] = g_ctrl.h[CT_LEVEL];
+    return GRX_OK;
+}
+
+int elem_grid(int64_t n)
+{
+    return (int)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(n, CL_BLOCK), 2048));
+}
+
+struct Args {
+    int64_t n;
+    const int64_t *row_ptr;
+    const int32_t *col;
+    const int32_t *hub_rows;
+    int64_t n_hub_rows, hub_degree;
+    const int32_t *sources;
+    int64_t n_sources;
+    int64_t *reach, *dsum;
+    double *harmonic;
+};
+
+template <int W>
+int run(const Args &a, const ClWs &ws, hipStream_t st)
+{
+    const int64_t n = a.n;
+    const unsigned row_blocks = (unsigned)std::max<int64_t>(
+        1, std::min<int64_t>(grx_ceil_div(n, CL_BLOCK / W), CL_MAX_ROW_BLOCKS));
+    const int64_t cells = n * W;
+    for (int64_t first = 0; first < a.n_sources; first += 64 * W) {
+        const int count = (int)std::min<int64_t>(64 * W, a.n_sources - first);
+        cl_zero_kernel<<<elem_grid(cells), CL_BLOCK, 0, st>>>(cells, ws.visited);
+        cl_zero_kernel<<<elem_grid(cells), CL_BLOCK, 0, st>>>(cells, ws.f0);
+        cl_source_init_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
+            n, W, count, a.sources + first, ws.visited, ws.f0, ws.ctrl);
+        GRX_LAUNCH_CHECK();
+        int32_t h[2] = {0, 0};
+        int64_t issued = 0;
+        while (!h[0]) {
+            // a BFS has at most n - 1 levels; one more launch finds the empty frontier
+            GRX_REQUIRE(issued <= n + 1, "grx_distance_sums: the BFS did not end after %lld levels",
+                        (long long)issued);
+            for (int k = 0; k < CL_LEVEL_BATCH; ++k, ++issued) {
+                if (a.n_hub_rows)
+                    cl_level_hub_kernel<W><<<(unsigned)a.n_hub_rows, CL_BLOCK, 0, st>>>(
+                        a.row_ptr, a.col, a.hub_rows, count, ws.visited, ws.f0, ws.f1, a.reach, a.dsum, ws.harm,
+                        ws.ctrl);
+                cl_level_kernel<W><<<row_blocks, CL_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.hub_degree, count,
+                                                                    ws.visited, ws.f0, ws.f1, a.reach, a.dsum,
+                                                                    ws.harm, ws.ctrl);
+                cl_finalize_kernel<<<1, 1, 0, st>>>(ws.ctrl);
+                GRX_LAUNCH_CHECK();
+            }
+            const int rc = read_ctrl(ws.ctrl, h, st);
+            if (rc != GRX_OK) return rc;
+        }
+    }
+    cl_harmonic_kernel<<<elem_grid(n), CL_BLOCK, 0, st>>>(n, ws.harm, a.harmonic);
+    GRX_LAUNCH_CHECK();
+    return GRX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t grx_distance_sums_workspace_bytes(int64_t n, int words, int64_t n_sources)
+{
+    return ws_bytes(n, choose_words(n, words, n_sources));
+}
+
+int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                      int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
+                      int64_t *d_reach, int64_t *d_dsum, double *d_harmonic, void *d_workspace,
+                      size_t workspace_bytes, void *stream)
+{
+    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_distance_sums: n = %lld out of range", (long long)n);
+    GRX_REQUIRE(d_row_ptr && d_col && d_reach && d_dsum && d_harmonic && d_workspace,
+                "grx_distance_sums: null pointer");
+    GRX_REQUIRE(n_sources >= 0 && n_sources < (int64_t)1 << 31 && (n_sources == 0 || d_sources),
+                "grx_distance_sums: source list");
+    GRX_REQUIRE(words == 0 || valid_words(words), "grx_distance_sums: words must be 0, 1, 2, 4, 8 or 16 (got %d)",
+                words);
+    GRX_REQUIRE(lanes_per_row >= 1, "grx_distance_sums: lanes_per_row must be >= 1");
+    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows), "grx_distance_sums: hub list");
+    const int W = choose_words(n, words, n_sources);
+    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, W), "grx_distance_sums: workspace %zu bytes, need %zu",
+                workspace_bytes, ws_bytes(n, W));
+    hipStream_t st = grx_stream(stream);
+    const ClWs ws = carve(d_workspace, n, W);
+    const Args a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
+                 d_sources, n_sources, d_reach, d_dsum, d_harmonic};
+    const int egrid = elem_grid(n);
+    cl_zero_kernel<<<egrid, CL_BLOCK, 0, st>>>(n, reinterpret_cast<uint64_t *>(d_reach));
+    cl_zero_kernel<<<egrid, CL_BLOCK, 0, st>>>(n, reinterpret_cast<uint64_t *>(d_dsum));
+    cl_zero_kernel<<<elem_grid(2 * n), CL_BLOCK, 0, st>>>(2 * n, ws.harm);
+    GRX_LAUNCH_CHECK();
+    switch (W) {
+    case 1: return run<1>(a, ws, st);
+    case 2: return run<2>(a, ws, st);
+    case 4: return run<4>(a, ws, st);
+    case 8: return run<8>(a, ws, st);
+    default: return run<16>(a, ws, st);
+    }
+}
+
+}  // extern "C"

@@ -1240,3 +1240,22 @@ def betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.nda
               csr_out.lanes_per_row, *in_args, _ptr(src), len(src), int(bool(endpoints)), float(scale), int(batch),
               _ptr(bc), _ptr(ws), ws_bytes, _stream())
     return bc
+
+
+def distance_sums(csr_pull: DeviceCSR, sources: np.ndarray,
+                  words: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """grx_distance_sums: (reach int64[n], dsum int64[n], harmonic fp64[n]) of the BFS from `sources` (internal row
+    ids) pulled over csr_pull -- the in-adjacency to walk out-arcs from each source, the out-adjacency to walk the
+    reversed arcs.  words = 64-bit source words per batch (1, 2, 4, 8 or 16; 0 = the library's choice)."""
+    n = csr_pull.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    lib = _lib.load()
+    ws_bytes = lib.grx_distance_sums_workspace_bytes(n, int(words), len(src))   # sized for the W the call uses
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    reach = torch.empty(max(n, 1), dtype=torch.int64, device=device())
+    dsum = torch.empty(max(n, 1), dtype=torch.int64, device=device())
+    harmonic = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    _lib.call('grx_distance_sums', n, _ptr(csr_pull.row_ptr), _ptr(csr_pull.col), _ptr(csr_pull.hub_rows),
+              csr_pull.n_hubs, csr_pull.lanes_per_row, _ptr(src), len(src), int(words), _ptr(reach), _ptr(dsum),
+              _ptr(harmonic), _ptr(ws), ws_bytes, _stream())
+    return reach, dsum, harmonic

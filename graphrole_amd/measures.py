@@ -4,8 +4,9 @@ Node measures for RolX sense making (Henderson et al., KDD 2012, section 4): the
 default arguments and is computed on the device CSR the feature extractor uses (graph/interface/base.py
 ``_device_graph``): degrees by grx_row_sums, clustering and effective size by grx_local_structure_measures on the
 triangle counts of grx_triangle_counts, PageRank and eigenvector centrality by the power iterations of
-csrc/grx_measures.hip, and betweenness centrality (opt-in: O(n m)) by the batched Brandes passes of
-csrc/grx_betweenness.hip.
+csrc/grx_measures.hip, betweenness centrality (opt-in: O(n m)) by the batched Brandes passes of
+csrc/grx_betweenness.hip, and closeness and harmonic centrality (opt-in: O(n m)) from the per-target distance sums of
+the bitset multi-source BFS of csrc/grx_closeness.hip.
 """
 from __future__ import annotations
 
@@ -30,10 +31,12 @@ CATALOGUE = {
     'eigenvector': "nx.eigenvector_centrality(G, max_iter=max_iter, tol=tol, weight='weight')",
     'betweenness_centrality': 'nx.betweenness_centrality(G, k=k, normalized=normalized, endpoints=endpoints, '
                               'seed=seed)',
+    'closeness_centrality': 'nx.closeness_centrality(G, wf_improved=wf_improved)',
+    'harmonic_centrality': 'nx.harmonic_centrality(G)',
 }
 
 #: catalogue entries computed only when named: not in ``available_measures`` nor in the default table
-OPT_IN = ('betweenness_centrality',)
+OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality')
 
 
 def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
@@ -83,7 +86,7 @@ def _count_csrs(graph, K, host):
 
 def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                   max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                  endpoints: bool = False) -> pd.DataFrame:
+                  endpoints: bool = False, wf_improved: bool = True) -> pd.DataFrame:
     """
     Node x measure table of well-known graph measures, computed on the GPU.
 
@@ -94,6 +97,8 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       (tol, max_iter)
     :param k, seed, normalized, endpoints: networkx's arguments of betweenness_centrality (see
       ``betweenness_centrality``); they apply to ``'betweenness_centrality'`` only
+    :param wf_improved: networkx's argument of closeness_centrality; it applies to ``'closeness_centrality'`` only.
+      ``'closeness_centrality'`` and ``'harmonic_centrality'`` named together share one multi-source BFS pass
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
     :raises ValueError: an unknown measure name
@@ -105,12 +110,12 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     ZeroDivisionError).
     """
     return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter, k=k, seed=seed,
-                       normalized=normalized, endpoints=endpoints)
+                       normalized=normalized, endpoints=endpoints, wf_improved=wf_improved)
 
 
 def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                 max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                endpoints: bool = False) -> pd.DataFrame:
+                endpoints: bool = False, wf_improved: bool = True) -> pd.DataFrame:
     """``node_measures`` on an existing graph adapter (its device CSR is built once and reused)."""
     directed = bool(graph.directed)
     multi = bool(getattr(graph, '_multi', False))
@@ -147,6 +152,12 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             cache['local'] = K.local_structure(out, K.triangle_counts(out), loops)
         return cache['local']
 
+    def distances():
+        # every node a source, walking the out-arcs: one pass for closeness and harmonic centrality
+        if 'distances' not in cache:
+            cache['distances'] = _distance_sums(graph, K, np.arange(host.n, dtype=np.int64), reverse=False)
+        return cache['distances']
+
     for nm in names:
         if nm == 'degree':
             col = counts('out') if not directed else K.add_columns(counts('out'), counts('in'))
@@ -172,6 +183,12 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col = K.betweenness(s_out, s_in if directed else None, np.asarray(host.inv)[sources], endpoints,
                                 _rescale_factor(host.n, normalized, directed, k, endpoints))
             dt = np.dtype('float64')
+        elif nm == 'closeness_centrality':
+            reach, dsum, _ = distances()
+            col = K.to_device(_closeness(K.to_host(reach)[:host.n], K.to_host(dsum)[:host.n], host.n, wf_improved))
+            dt = np.dtype('float64')
+        elif nm == 'harmonic_centrality':
+            col, dt = distances()[2], np.dtype('float64')
         elif nm == 'pagerank':
             col, iterations[nm] = K.pagerank(tr if directed else out, K.row_sums(out, False), alpha, tol, max_iter)
             dt = np.dtype('float64')
@@ -205,11 +222,7 @@ def _betweenness_sources(graph, k: Optional[int], seed) -> np.ndarray:
         if isinstance(k, bool) or not isinstance(k, Integral) or not 1 <= k <= len(nodes):
             raise ValueError(f'k must be an integer in 1..{len(nodes)} (the number of nodes), got {k!r}')
         nodes = _py_random_state(seed).sample(nodes, int(k))
-    labels = graph.to_csr().labels
-    if isinstance(labels, range) and labels == range(len(labels)):
-        return np.asarray(nodes, dtype=np.int64)
-    row_of = {label: i for i, label in enumerate(labels)}
-    return np.fromiter((row_of[v] for v in nodes), dtype=np.int64, count=len(nodes))
+    return _rows_of(graph, nodes)
 
 
 def _rescale_factor(n: int, normalized: bool, directed: bool, k: Optional[int], endpoints: bool) -> float:
@@ -255,3 +268,136 @@ def betweenness_centrality(G, k: Optional[int] = None, normalized: bool = True, 
                                   f'Dijkstra-based and not implemented here; use networkx')
     frame = node_measures(G, ['betweenness_centrality'], k=k, seed=seed, normalized=normalized, endpoints=endpoints)
     return frame['betweenness_centrality']
+
+
+def _rows_of(graph, nodes) -> np.ndarray:
+    """Rows of ``graph.to_csr()`` (sorted labels) of the node labels `nodes`, in that order."""
+    labels = graph.to_csr().labels
+    if isinstance(labels, range) and labels == range(len(labels)):
+        return np.asarray(nodes, dtype=np.int64)
+    row_of = {label: i for i, label in enumerate(labels)}
+    return np.fromiter((row_of[v] for v in nodes), dtype=np.int64, count=len(nodes))
+
+
+def _distance_sums(graph, K, sources: np.ndarray, reverse: bool):
+    """kernels.distance_sums from `sources` (internal row ids) along the distinct arcs (``_structure_csrs``: G[v],
+    parallel edges once): the out-arcs (pulled over the in-adjacency), or with `reverse` the reversed arcs (pulled over
+    the out-adjacency)."""
+    s_out, s_in = graph._structure_csrs()
+    if not graph.directed or reverse:
+        return K.distance_sums(s_out, sources)
+    if s_in is None:
+        raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; closeness and '
+                                  f'harmonic centrality cannot be computed on it')
+    return K.distance_sums(s_in, sources)
+
+
+def _closeness(reach: np.ndarray, dsum: np.ndarray, n: int, wf_improved: bool) -> np.ndarray:
+    """networkx's closeness from len(sp) - 1 = reach and totsp = dsum, with its own IEEE operations:
+    (len(sp) - 1.0) / totsp, then *= (len(sp) - 1.0) / (len(G) - 1); 0.0 unless totsp > 0 and len(G) > 1."""
+    r = np.asarray(reach, dtype=np.int64).astype(np.float64)
+    t = np.asarray(dsum, dtype=np.int64).astype(np.float64)
+    ok = (t > 0) & (n > 1)
+    c = np.zeros(len(r))
+    c[ok] = r[ok] / t[ok]
+    if wf_improved and n > 1:
+        c[ok] *= r[ok] / float(n - 1)
+    return c
+
+
+def _distance_arguments(name: str, distance) -> None:
+    if distance is not None:
+        raise NotImplementedError(f'weighted distances (nx.{name}(G, distance={distance!r})) need a shortest-path '
+                                  f'search by weight and are not implemented here; use networkx')
+
+
+def _node_set(graph, nbunch) -> list:
+    """networkx's ``set(G.nbunch_iter(nbunch))``: every node for None, the node itself for a node, else the members
+    of the iterable that are nodes (others are dropped)."""
+    nodes = list(graph.get_nodes())
+    if nbunch is None:
+        return nodes
+    members = set(nodes)
+    try:
+        if nbunch in members:
+            return [nbunch]
+    except TypeError:                                          # unhashable: a container of nodes
+        pass
+    import networkx as nx
+    try:
+        items = list(iter(nbunch))
+    except TypeError as exc:
+        raise nx.NetworkXError('nbunch is not a node or a sequence of nodes.') from exc
+    try:
+        return list(dict.fromkeys(v for v in items if v in members))
+    except TypeError as exc:
+        raise nx.NetworkXError(f'Node {exc} in sequence nbunch is not a valid node.') from exc
+
+
+def closeness_centrality(G, u=None, distance=None, wf_improved: bool = True):
+    """
+    Closeness centrality on the GPU: networkx 3.4.2's ``closeness_centrality(G, u, distance=None, wf_improved)``
+    (closeness.py:107-137) from the per-target distance sums of csrc/grx_closeness.hip (a bitset multi-source BFS,
+    up to 1 024 sources per pass).
+
+    :param G: any graph ``node_measures`` accepts; multigraph edges count once, self-loops never shorten a path
+    :param u: None = every node (every node is a BFS source; for a directed graph the distances d(v, u) run INTO u,
+      as networkx's ``G.reverse()``); a node = that node only, one BFS along the reversed arcs
+    :param distance: must be None (weighted distances need a shortest-path search by weight, not implemented here)
+    :param wf_improved: as networkx: scale by the fraction of the other nodes that reach u
+    :return: float64 Series indexed by the sorted node labels (the index of ``node_measures``), or a float for `u`
+    :raises NotImplementedError: distance is not None
+    :raises networkx.NodeNotFound: u is not a node
+
+    Bit-equal to networkx: len(sp) - 1 and totsp are exact integer sums, and the value is formed from them with
+    networkx's own three IEEE operations.
+    """
+    _distance_arguments('closeness_centrality', distance)
+    if u is None:
+        return node_measures(G, ['closeness_centrality'], wf_improved=wf_improved)['closeness_centrality']
+    graph = _adapter(G)
+    if u not in set(graph.get_nodes()):
+        import networkx as nx
+        raise nx.NodeNotFound(f'Source {u} is not in G')
+    K = graph._K()
+    host = graph._device_graph()[0]
+    source = np.asarray(host.inv)[_rows_of(graph, [u])]
+    reach, dsum, _ = _distance_sums(graph, K, source, reverse=True)
+    r = int(K.to_host(reach)[:host.n].sum())
+    t = int(K.to_host(dsum)[:host.n].sum())
+    return float(_closeness(np.array([r]), np.array([t]), host.n, wf_improved)[0])
+
+
+def harmonic_centrality(G, nbunch=None, distance=None, sources=None) -> pd.Series:
+    """
+    Harmonic centrality on the GPU: networkx 3.4.2's ``harmonic_centrality(G, nbunch, distance=None, sources)``
+    (harmonic.py:68-89), the sum of 1 / d(v, u) over the sources v that reach u along the out-arcs, from the
+    per-target distance sums of csrc/grx_closeness.hip.
+
+    :param G: any graph ``node_measures`` accepts; multigraph edges count once, self-loops never shorten a path
+    :param nbunch: the nodes to return (networkx's ``G.nbunch_iter``: a node, an iterable whose non-members are
+      dropped, or None = every node)
+    :param distance: must be None (weighted distances need a shortest-path search by weight, not implemented here)
+    :param sources: the BFS sources, likewise (duplicates count once)
+    :return: float64 Series named ``harmonic_centrality`` indexed by the sorted members of `nbunch`
+    :raises NotImplementedError: distance is not None
+
+    Each value is the correctly rounded sum of the fp64 terms 1 / d (an exact fixed-point sum, rounded once), the same
+    bits for every source order and run; networkx adds the terms one by one, so the two agree to 1e-12 relative.
+    networkx runs the BFS from `nbunch` instead (along the reversed arcs) when it is smaller than `sources`; here the
+    BFS always runs from `sources`: the same value, possibly more work, and only the rounding differs.
+    """
+    _distance_arguments('harmonic_centrality', distance)
+    graph = _adapter(G)
+    targets = _node_set(graph, nbunch)
+    K = graph._K()
+    host = graph._device_graph()[0]
+    if sources is None:
+        rows = np.arange(host.n, dtype=np.int64)
+    else:
+        rows = np.sort(np.asarray(host.inv)[_rows_of(graph, _node_set(graph, sources))])
+    _, _, harmonic = _distance_sums(graph, K, rows, reverse=False)
+    series = graph._frame(['harmonic_centrality'], [harmonic], [np.dtype('float64')])['harmonic_centrality']
+    if nbunch is None:
+        return series
+    return series[series.index.isin(targets)]

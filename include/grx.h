@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define GRX_VERSION 800          /* 0.8.0: grx_betweenness (unweighted betweenness centrality of the sense-making measures)
+#define GRX_VERSION 900          /* 0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
+                                    measures)
+                                    0.8.0: grx_betweenness (unweighted betweenness centrality of the sense-making measures)
                                     0.7.0: node measures of RolX sense making (grx_pagerank, grx_eigenvector_centrality,
                                     grx_local_structure_measures) and grx_host_nnls; status GRX_ERR_NOT_CONVERGED */
 #define GRX_MAX_BINS 128         /* upper bound on vertical-log bins (n < 2^63 gives < 70) */
@@ -843,6 +845,36 @@ int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
                     const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
                     const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch, double *d_bc,
                     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_distance_sums: per-target BFS distance sums from many sources -- what networkx.closeness_centrality(G, u,
+ *   distance=None, wf_improved) (closeness.py:107-137) and networkx.harmonic_centrality(G, nbunch, distance=None,
+ *   sources) (harmonic.py:68-89) compute from.  For every node v and the sources s = d_sources[0 .. n_sources)
+ *   (int32 row ids; a repeated id counts once per occurrence) along the arcs the caller lists:
+ *     reach[v]    = number of sources s != v with a path s -> v                       (networkx: len(sp) - 1)
+ *     dsum[v]     = sum of d(s, v) over those sources                                 (networkx: totsp)
+ *     harmonic[v] = sum of fl(1 / d(s, v)) over those sources, correctly rounded      (networkx: sum of 1 / d)
+ *   The BFS PULLS over d_row_ptr / d_col: next(v) collects the frontier of the nodes listed in v's row.  So pass the
+ *   in-adjacency (transposed CSR) to walk the out-arcs from each source -- closeness of every node and harmonic
+ *   centrality -- and the out-adjacency to walk the reversed arcs from one source (closeness(G, u): networkx walks
+ *   G.reverse()); an undirected graph's CSR is both.  Weights are not read; self-loops and parallel arcs never change
+ *   a distance.  Rows longer than GRX_HUB_FACTOR * lanes_per_row must be listed in d_hub_rows.
+ *   Method: a bitset multi-source BFS (Then et al., VLDB 2014), S = 64 words sources per batch; per node three masks
+ *   of `words` uint64 (visited and two frontiers: state 24 n words bytes).  words: 1, 2, 4, 8 or 16; 0 = the
+ *   library's choice: the narrowest power of two that holds the source list, at most the widest one up to 16 whose
+ *   state fits 4 GiB, and at least 1.
+ *   Exact: reach and dsum are integer sums (dsum <= n^2 < 2^62); harmonic is summed in a 128-bit fixed-point integer
+ *   (fl(1 / d) is a whole multiple of 2^-84 for d < 2^31) and rounded once to nearest-even, so every output has the
+ *   same bits for every `words`, source order and run.  networkx's closeness follows bit for bit from reach and dsum
+ *   (its own three IEEE operations); networkx's harmonic adds the same terms one by one, so it agrees to 1e-12.
+ *   d_reach, d_dsum: int64[n], d_harmonic: fp64[n], all overwritten.  n < 2^31.
+ *   d_workspace: grx_distance_sums_workspace_bytes(n, words, n_sources) bytes.
+ */
+size_t grx_distance_sums_workspace_bytes(int64_t n, int words, int64_t n_sources);
+int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                      int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
+                      int64_t *d_reach, int64_t *d_dsum, double *d_harmonic, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
