@@ -1148,7 +1148,7 @@ def row_counts(csr: DeviceCSR, add_self_loop: bool) -> torch.Tensor:
 
 
 def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alpha: float, tol: float,
-           max_iter: int) -> Tuple[torch.Tensor, int]:
+           max_iter: int, lanes: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     n = csr_in.n
     lib = _lib.load()
     ws_bytes = getattr(lib, name + '_workspace_bytes')(n)
@@ -1156,7 +1156,14 @@ def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alp
     x = torch.empty(max(n, 1), dtype=torch.float64, device=device())
     iters = ctypes.c_int(0)
     graph = (n, _ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.w))
-    hubs = (_ptr(csr_in.hub_rows), csr_in.n_hubs, csr_in.lanes_per_row)
+    hub_rows, n_hubs, lanes_per_row = csr_in.hub_rows, csr_in.n_hubs, csr_in.lanes_per_row
+    if lanes is not None and int(lanes) != lanes_per_row:
+        # the kernels read hacc[v] for every row longer than 32 * lanes: the hub list must be the one of this width
+        lanes_per_row = int(lanes)
+        rows = np.nonzero(np.diff(csr_in._host[0]) > HUB_FACTOR * lanes_per_row)[0].astype(np.int32)
+        n_hubs = int(len(rows))
+        hub_rows = torch.from_numpy(rows).to(device()) if n_hubs else None
+    hubs = (_ptr(hub_rows), n_hubs, lanes_per_row)
     if name == 'grx_pagerank':
         args = graph + (_ptr(out_weight),) + hubs + (float(alpha), float(tol))
     else:
@@ -1170,14 +1177,16 @@ def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alp
 
 
 def pagerank(csr_in: DeviceCSR, out_weight: torch.Tensor, alpha: float, tol: float,
-             max_iter: int) -> Tuple[torch.Tensor, int]:
-    """grx_pagerank over the in-adjacency csr_in; out_weight = out-weight row sums.  (x, iterations)."""
-    return _power('grx_pagerank', csr_in, out_weight, alpha, tol, max_iter)
+             max_iter: int, lanes: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """grx_pagerank over the in-adjacency csr_in; out_weight = out-weight row sums.  (x, iterations).
+    lanes = lanes per row (4, 8, 16 or 32; None = csr_in.lanes_per_row), with the hub list of that width."""
+    return _power('grx_pagerank', csr_in, out_weight, alpha, tol, max_iter, lanes)
 
 
-def eigenvector_centrality(csr_in: DeviceCSR, tol: float, max_iter: int) -> Tuple[torch.Tensor, int]:
-    """grx_eigenvector_centrality over the in-adjacency csr_in.  (x, iterations)."""
-    return _power('grx_eigenvector_centrality', csr_in, None, 0.0, tol, max_iter)
+def eigenvector_centrality(csr_in: DeviceCSR, tol: float, max_iter: int,
+                           lanes: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """grx_eigenvector_centrality over the in-adjacency csr_in.  (x, iterations).  lanes: as in ``pagerank``."""
+    return _power('grx_eigenvector_centrality', csr_in, None, 0.0, tol, max_iter, lanes)
 
 
 def local_structure(csr: DeviceCSR, T: torch.Tensor, has_loops: bool) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1,14 +1,16 @@
 """
 RolX sense making on the MI355X: graphrole_amd.node_measures against networkx 3.4.2 computed here (degrees,
 clustering and effective size bit-equal; PageRank and eigenvector centrality to 1e-12 relative with the iteration
-count of tests/sense_oracle.py's restatement of networkx's loops), and RoleExtractor.sense_making end to end.
+count of tests/sense_oracle.py's restatement of networkx's loops; at 1 M nodes the eigenvector against the long-double
+oracle of tests/measures_oracle.py), and RoleExtractor.sense_making end to end.
 """
 import networkx as nx
 import numpy as np
 import pandas as pd
 import pytest
 
-from tests import sense_oracle
+from tests import measures_oracle, sense_oracle
+from tests.test_gpu_closeness import _directed_hubs, _disconnected
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +57,23 @@ def _multigraph():
     return G
 
 
+def _multidigraph():
+    G = nx.MultiDiGraph()
+    G.add_edges_from([(0, 1), (0, 1), (1, 0), (1, 2), (2, 0), (2, 3), (3, 3), (3, 3), (3, 4), (4, 5), (5, 3), (5, 3),
+                      (5, 3), (6, 5)])
+    G.add_edge(1, 2, weight=2.5)
+    G.add_node(7)
+    return G
+
+
+def _directed_hubs_weighted(seed=12):
+    G = _directed_hubs()                                        # in-hub 0, out-hub 1 (tests/test_gpu_closeness.py)
+    rng = np.random.default_rng(seed)
+    for u, v in G.edges:
+        G[u][v]['weight'] = float(rng.uniform(0.1, 4.0))
+    return G
+
+
 GRAPHS = {
     'karate': lambda: nx.karate_club_graph(),
     'er300': lambda: nx.gnm_random_graph(300, 1500, seed=1),
@@ -65,14 +84,22 @@ GRAPHS = {
     'loops_isolated': _loops_isolated,
     'strings': _strings,
     'multigraph': _multigraph,
+    'multidigraph': _multidigraph,
+    'star1500': lambda: nx.star_graph(1500),
+    'directed_hubs_weighted': _directed_hubs_weighted,
+    'disconnected': _disconnected,
 }
+
+# networkx's default max_iter = 100 unless the graph needs more: the eigenvector iteration of a star contracts by
+# (sqrt(n) - 1) / (sqrt(n) + 1) per step
+MAX_ITER = {'star1500': 1000}
 
 
 def _series(d, index):
     return np.array([d[k] for k in index], dtype=np.float64)
 
 
-def _expected(G, name, index):
+def _expected(G, name, index, max_iter=100):
     if name == 'degree':
         return _series(dict(G.degree()), index), None
     if name == 'weighted_degree':
@@ -91,10 +118,10 @@ def _expected(G, name, index):
         d.update({v: np.nan for v in own})
         return _series(d, index), None
     if name == 'pagerank':
-        x, it = sense_oracle.pagerank(G)
-        assert np.allclose(_series(x, index), _series(nx.pagerank(G), index), rtol=1e-12, atol=0)
+        x, it = sense_oracle.pagerank(G, max_iter=max_iter)
+        assert np.allclose(_series(x, index), _series(nx.pagerank(G, max_iter=max_iter), index), rtol=1e-12, atol=0)
         return _series(x, index), it
-    x, it = sense_oracle.eigenvector(G)
+    x, it = sense_oracle.eigenvector(G, max_iter=max_iter)
     return _series(x, index), it
 
 
@@ -102,7 +129,8 @@ def _expected(G, name, index):
 def test_node_measures_match_networkx(key):
     from graphrole_amd import node_measures
     G = GRAPHS[key]()
-    M = node_measures(G)
+    max_iter = MAX_ITER.get(key, 100)
+    M = node_measures(G) if max_iter == 100 else node_measures(G, max_iter=max_iter)
     index = sorted(G.nodes)
     assert list(M.index) == index
     directed, multi = G.is_directed(), G.is_multigraph()
@@ -111,7 +139,7 @@ def test_node_measures_match_networkx(key):
         + ([] if multi else ['eigenvector'])
     assert list(M.columns) == expected_cols
     for name in M.columns:
-        want, it = _expected(G, name, index)
+        want, it = _expected(G, name, index, max_iter)
         got = M[name].to_numpy(dtype=np.float64)
         if name in ('pagerank', 'eigenvector'):
             assert M.attrs['iterations'][name] == it, (name, M.attrs['iterations'][name], it)
@@ -164,6 +192,13 @@ def test_non_convergence_raises():
     assert isinstance(info.value, RuntimeError)
     with pytest.raises(ConvergenceError):
         node_measures(G, ['eigenvector'], max_iter=2)
+    # networkx's own defaults do not converge on the star: the same error, after the same 100 iterations
+    star = GRAPHS['star1500']()
+    with pytest.raises(nx.PowerIterationFailedConvergence):
+        nx.eigenvector_centrality(star)
+    with pytest.raises(ConvergenceError) as info:
+        node_measures(star, ['eigenvector'])
+    assert info.value.iterations == 100
 
 
 def test_fullsize_ba_pagerank_and_clustering():
@@ -175,6 +210,21 @@ def test_fullsize_ba_pagerank_and_clustering():
     assert M.attrs['iterations']['pagerank'] == it
     np.testing.assert_allclose(M['pagerank'].to_numpy(), x, rtol=1e-12, atol=0)
     assert np.array_equal(M['clustering'].to_numpy(), sense_oracle.clustering_arrays(g))
+
+
+def test_fullsize_ba_eigenvector():
+    """ev_iter_kernel and ev_normalize_kernel at 1 M nodes (their grid-stride loops take a second trip) against the
+    long-double oracle; the same 1e-12 and the same iteration count."""
+    from graphrole_amd import node_measures, synth
+    g = synth.ba_graph(1_000_000, 10, seed=0)
+    M = node_measures(g, ['eigenvector'])
+    x, it, errs = measures_oracle.eigenvector_ld(g.row_ptr, g.col, g.w)
+    thresh = g.n * 1e-6
+    assert min(abs(float(e) / thresh - 1.0) for e in errs[-2:]) > 1e-6      # the count cannot flip under rounding
+    assert M.attrs['iterations']['eigenvector'] == it
+    got = M['eigenvector'].to_numpy()
+    print(f'fullsize eigenvector: iterations {it}, max relative deviation {measures_oracle.max_rel_dev(got, x):.3e}')
+    np.testing.assert_allclose(got.astype(np.longdouble), x, rtol=1e-12, atol=0)
 
 
 def test_karate_end_to_end_sense_making():

@@ -59,7 +59,7 @@ def _in_matrix(csr):
     return A                                                  # A[v, u] = weight of u -> v (pulled rows)
 
 
-def _pagerank(csr_in, out_weight, alpha, tol, max_iter):
+def _pagerank(csr_in, out_weight, alpha, tol, max_iter, lanes=None):
     from graphrole_amd import ConvergenceError
     A = _in_matrix(csr_in)
     S = out_weight.numpy()
@@ -74,7 +74,7 @@ def _pagerank(csr_in, out_weight, alpha, tol, max_iter):
     raise ConvergenceError('not converged', iterations=max_iter)
 
 
-def _eigenvector(csr_in, tol, max_iter):
+def _eigenvector(csr_in, tol, max_iter, lanes=None):
     from graphrole_amd import ConvergenceError
     A = _in_matrix(csr_in)
     n = csr_in.n
