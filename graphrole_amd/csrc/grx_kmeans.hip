@@ -1918,9 +1918,14 @@ int grx_transpose(int64_t rows, int64_t cols, const double *d_in, int64_t ld_in,
 {
     GRX_REQUIRE(rows >= 0 && cols >= 0 && ld_in >= cols && ld_out >= rows, "grx_transpose: bad shape");
     if (rows == 0 || cols == 0) return GRX_OK;
+    // rows = n at the callers (roles/factor.py), so grid.y passes 65 535 workgroups at n > 2 097 120: the MI355X runtime
+    // takes such a launch (tests/test_gpu_aggx_kernels.py::test_transpose_tall runs 65 538); what must not happen is a
+    // tile count that the 32-bit grid dimensions cut short
+    const int64_t col_tiles = grx_ceil_div(cols, 32), row_tiles = grx_ceil_div(rows, 32);
+    GRX_REQUIRE(col_tiles <= 0x7fffffff && row_tiles <= 0x7fffffff, "grx_transpose: %lld x %lld beyond the 32-bit grid",
+                (long long)rows, (long long)cols);
     GRX_REQUIRE(d_in && d_out, "grx_transpose: NULL pointer");
-    const dim3 grid((unsigned)grx_ceil_div(cols, 32), (unsigned)grx_ceil_div(rows, 32));
-    GRX_REQUIRE(grid.y < 65536u * 1u || true, "grx_transpose: too many rows");
+    const dim3 grid((unsigned)col_tiles, (unsigned)row_tiles);
     km_transpose_kernel<<<grid, 256, 0, grx_stream(stream)>>>(rows, cols, d_in, ld_in, d_out, ld_out);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
