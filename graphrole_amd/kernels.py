@@ -1268,3 +1268,23 @@ def distance_sums(csr_pull: DeviceCSR, sources: np.ndarray,
               csr_pull.n_hubs, csr_pull.lanes_per_row, _ptr(src), len(src), int(words), _ptr(reach), _ptr(dsum),
               _ptr(harmonic), _ptr(ws), ws_bytes, _stream())
     return reach, dsum, harmonic
+
+
+def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor],
+                                                                    Optional[torch.Tensor], int]:
+    """grx_biconnected on the symmetric CSR of an undirected graph's distinct arcs: (count int64[n] = the number of
+    biconnected components of every row, parent int32[n] = the BFS forest (-1 for a root), label int32[n] = the
+    component of the tree edge (parent[c], c) (-1 for a root), n_components).  want_forest=False passes NULL for
+    parent and label (both None then)."""
+    n = csr.n
+    lib = _lib.load()
+    ws_bytes = lib.grx_biconnected_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    count = torch.empty(max(n, 1), dtype=torch.int64, device=device())
+    parent = torch.empty(max(n, 1), dtype=torch.int32, device=device()) if want_forest else None
+    label = torch.empty(max(n, 1), dtype=torch.int32, device=device()) if want_forest else None
+    n_components = ctypes.c_int64(0)
+    _lib.call('grx_biconnected', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(csr.hub_rows), csr.n_hubs,
+              csr.lanes_per_row, _ptr(count), _ptr(parent), _ptr(label), ctypes.byref(n_components), _ptr(ws), ws_bytes,
+              _stream())
+    return count, parent, label, int(n_components.value)

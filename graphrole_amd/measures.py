@@ -6,7 +6,8 @@ default arguments and is computed on the device CSR the feature extractor uses (
 triangle counts of grx_triangle_counts, PageRank and eigenvector centrality by the power iterations of
 csrc/grx_measures.hip, betweenness centrality (opt-in: O(n m)) by the batched Brandes passes of
 csrc/grx_betweenness.hip, and closeness and harmonic centrality (opt-in: O(n m)) from the per-target distance sums of
-the bitset multi-source BFS of csrc/grx_closeness.hip.
+the bitset multi-source BFS of csrc/grx_closeness.hip, and the number of biconnected components of every node (opt-in;
+more than one: an articulation point) by the Tarjan-Vishkin sweeps of csrc/grx_biconnected.hip.
 """
 from __future__ import annotations
 
@@ -33,10 +34,13 @@ CATALOGUE = {
                               'seed=seed)',
     'closeness_centrality': 'nx.closeness_centrality(G, wf_improved=wf_improved)',
     'harmonic_centrality': 'nx.harmonic_centrality(G)',
+    'biconnected_components': 'Counter(v for c in nx.biconnected_components(G) for v in c)',
 }
 
-#: catalogue entries computed only when named: not in ``available_measures`` nor in the default table
-OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality')
+#: catalogue entries computed only when named: not in ``available_measures`` nor in the default table -- the
+#: centralities because they cost O(n m), 'biconnected_components' (O(n + m) per sweep) because the default table and
+#: ``available_measures`` are pinned as they were before it existed
+OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality', 'biconnected_components')
 
 
 def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
@@ -52,6 +56,8 @@ def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
                     f'use {CATALOGUE[name]} from networkx')
     if name == 'eigenvector' and multi:
         return f'networkx does not implement {CATALOGUE[name]} for a multigraph'
+    if name == 'biconnected_components' and directed:
+        return f'networkx does not implement nx.biconnected_components(G) for a {kind}'
     return None
 
 
@@ -102,8 +108,9 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
     :raises ValueError: an unknown measure name
-    :raises NotImplementedError: a measure that networkx does not implement for this kind of graph, or that is
-      outside this implementation's scope (directed / multigraph clustering and effective size)
+    :raises NotImplementedError: a measure that networkx does not implement for this kind of graph (among them
+      ``'biconnected_components'`` of a directed graph), or that is outside this implementation's scope (directed /
+      multigraph clustering and effective size)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
 
     Stated divergence: ``effective_size`` of a node whose only neighbour is itself is NaN (networkx raises
@@ -158,6 +165,12 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             cache['distances'] = _distance_sums(graph, K, np.arange(host.n, dtype=np.int64), reverse=False)
         return cache['distances']
 
+    def blocks():
+        # the undirected graph's distinct arcs: parallel edges count once
+        if 'blocks' not in cache:
+            cache['blocks'] = K.biconnected(graph._structure_csrs()[0])
+        return cache['blocks']
+
     for nm in names:
         if nm == 'degree':
             col = counts('out') if not directed else K.add_columns(counts('out'), counts('in'))
@@ -189,6 +202,8 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             dt = np.dtype('float64')
         elif nm == 'harmonic_centrality':
             col, dt = distances()[2], np.dtype('float64')
+        elif nm == 'biconnected_components':
+            col, dt = blocks()[0], np.dtype('int64')
         elif nm == 'pagerank':
             col, iterations[nm] = K.pagerank(tr if directed else out, K.row_sums(out, False), alpha, tol, max_iter)
             dt = np.dtype('float64')
@@ -401,3 +416,66 @@ def harmonic_centrality(G, nbunch=None, distance=None, sources=None) -> pd.Serie
     if nbunch is None:
         return series
     return series[series.index.isin(targets)]
+
+
+def _undirected_adapter(G, what: str):
+    graph = _adapter(G)
+    if graph.directed:
+        raise NotImplementedError(f'networkx does not implement nx.{what}(G) for a directed graph')
+    return graph
+
+
+def biconnected_component_counts(G) -> pd.Series:
+    """
+    The number of biconnected components every node belongs to, on the GPU: ``Counter(v for c in
+    nx.biconnected_components(G) for v in c)`` of networkx 3.4.2 (components/biconnected.py), by the Tarjan-Vishkin
+    sweeps of csrc/grx_biconnected.hip.  More than one: the node is an articulation point; 0: it has no edge but
+    (possibly) a self-loop.
+
+    :param G: any undirected graph ``node_measures`` accepts; multigraph edges count once, self-loops are ignored
+    :return: int64 Series named ``biconnected_components`` indexed by the sorted node labels; equal to networkx's
+      counts (nodes networkx's Counter leaves out are 0 here)
+    :raises NotImplementedError: G is directed (as networkx)
+    """
+    return node_measures(G, ['biconnected_components'])['biconnected_components']
+
+
+def articulation_points(G) -> list:
+    """
+    The articulation points of an undirected graph -- the nodes that lie in more than one biconnected component -- as
+    ``nx.articulation_points(G)``, from ``biconnected_component_counts``.
+
+    :return: list of node labels in index order (sorted labels).  Stated divergence: networkx yields the same nodes in
+      the order its depth-first search meets them, which it does not specify
+    :raises NotImplementedError: G is directed (as networkx)
+    """
+    counts = biconnected_component_counts(G)
+    return list(counts.index[counts.to_numpy() > 1])
+
+
+def biconnected_components(G) -> list:
+    """
+    The biconnected components of an undirected graph as ``list(nx.biconnected_components(G))``: a list of node-label
+    sets, rebuilt on the host from the BFS forest and the per-tree-edge component labels of csrc/grx_biconnected.hip
+    (component r is the union of {c, parent[c]} over the tree edges with label[c] = r) by one numpy group-by.
+
+    :return: list of sets; the order of the list is unspecified, as in networkx.  Isolated nodes are in no component
+    :raises NotImplementedError: G is directed (as networkx)
+    """
+    graph = _undirected_adapter(G, 'biconnected_components')
+    K = graph._K()
+    host = graph._device_graph()[0]
+    _, parent, label, n_components = K.biconnected(graph._structure_csrs()[0])
+    parent = np.asarray(K.to_host(parent))[:host.n].astype(np.int64)
+    label = np.asarray(K.to_host(label))[:host.n].astype(np.int64)
+    child = np.nonzero(parent >= 0)[0]
+    # (component, member) pairs of both ends of every tree edge, distinct and grouped by component
+    pairs = np.unique(np.stack([np.concatenate([label[child], label[child]]),
+                                np.concatenate([child, parent[child]])], axis=1), axis=0)
+    members = np.asarray(host.perm)[pairs[:, 1]]                # internal row -> row of the sorted labels
+    cuts = np.nonzero(np.diff(pairs[:, 0]))[0] + 1
+    labels = graph.to_csr().labels
+    plain = isinstance(labels, range) and labels == range(len(labels))
+    groups = np.split(members, cuts) if len(members) else []
+    assert len(groups) == n_components
+    return [set(g.tolist()) if plain else {labels[i] for i in g.tolist()} for g in groups]

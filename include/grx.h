@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define GRX_VERSION 900          /* 0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
+#define GRX_VERSION 1000         /* 0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
+                                    sense-making measures)
+                                    0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
                                     measures)
                                     0.8.0: grx_betweenness (unweighted betweenness centrality of the sense-making measures)
                                     0.7.0: node measures of RolX sense making (grx_pagerank, grx_eigenvector_centrality,
@@ -875,6 +877,35 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
                       int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
                       int64_t *d_reach, int64_t *d_dsum, double *d_harmonic, void *d_workspace,
                       size_t workspace_bytes, void *stream);
+
+/*
+ * grx_biconnected: for every node of an undirected graph the number of biconnected components it belongs to -- what
+ *   Counter(v for c in networkx.biconnected_components(G) for v in c) counts, and more than one exactly for the nodes
+ *   of networkx.articulation_points(G) (networkx/algorithms/components/biconnected.py: biconnected_components,
+ *   articulation_points; both a depth-first search) -- together with a spanning forest and a component label per tree
+ *   edge from which the components themselves follow.
+ *   d_row_ptr / d_col: the CSR of the graph's distinct arcs, symmetric (every edge from both ends), rows in any order;
+ *   self-loop entries are skipped, weights are not read.  Rows longer than GRX_HUB_FACTOR * lanes_per_row must be
+ *   listed in d_hub_rows.
+ *   Method: Tarjan-Vishkin (SIAM J. Comput. 1985) on a BFS spanning forest, level-synchronous: connected components
+ *   by lock-free union-find (roots = the smallest id of each component), a BFS from every root at once, subtree sizes,
+ *   preorder numbers, low / high over the non-tree edges, then a second union-find over the tree edges; see the header
+ *   of csrc/grx_biconnected.hip.  O(n + m) work per sweep and O(D) launches for BFS depth D; the level count is read
+ *   back once per 8 levels.  A deep graph (a path) is bound by launch latency.
+ *   d_count:  int64[n], overwritten; 0 for an isolated node and for a node whose only arc is a self-loop.
+ *   d_parent: int32[n] or NULL: the BFS forest, parent[v] = the smallest id among v's neighbours one level nearer to
+ *             the root, -1 for a root (the smallest id of its connected component).  The same in every run.
+ *   d_label:  int32[n] or NULL: label[c] names the biconnected component of the tree edge (parent[c], c) -- the
+ *             smallest c among the component's tree edges -- and is -1 for a root.  Component r is the union of
+ *             {c, parent[c]} over the c with label[c] = r.
+ *   n_components: HOST int64 or NULL: the number of biconnected components (reading it waits for the stream).
+ *   Exact (integers only; integer atomics whose results do not depend on their order): every output has the same
+ *   bits in every run.  n < 2^31.  d_workspace: grx_biconnected_workspace_bytes(n) bytes (about 40 n).
+ */
+size_t grx_biconnected_workspace_bytes(int64_t n);
+int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                    int64_t n_hub_rows, int lanes_per_row, int64_t *d_count, int32_t *d_parent, int32_t *d_label,
+                    int64_t *n_components, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
