@@ -14,7 +14,8 @@ def __getattr__(name):
         from .roles.extract import RoleExtractor
         return RoleExtractor
     if name in ('node_measures', 'betweenness_centrality', 'closeness_centrality', 'harmonic_centrality',
-                'biconnected_component_counts', 'articulation_points', 'biconnected_components', 'ConvergenceError'):
+                'biconnected_component_counts', 'articulation_points', 'biconnected_components', 'core_number',
+                'onion_layers', 'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     raise AttributeError(name)

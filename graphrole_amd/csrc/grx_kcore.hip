@@ -1,0 +1,387 @@
+// grx_kcore.hip -- core number and onion layer of every node for RolX sense making: networkx 3.4.2's core_number
+// (core.py: Batagelj-Zaversnik bucket peeling, sequential) and onion_layers (Hebert-Dufresne et al., "Multi-scale
+// structure and topological anomaly detection via a new network statistic: the onion decomposition", 2016), both from
+// one synchronous peeling:
+//
+//   k = 0, layer = 1, every node alive, deg(v) = degree of v (directed: in + out)
+//   while a node is alive:
+//       k = max(k, min deg over the alive nodes)
+//       F = {alive v : deg(v) <= k}                  decided on the degrees at the start of the round
+//       core(v) = k, onion(v) = layer for v in F; F leaves
+//       for v in F, for every arc between v and a node u: deg(u) -= 1
+//       layer += 1
+//
+// The frontier is a list, not a scan.  A node that is alive and outside F at the start of a round has deg > k, so the
+// F of the next round is exactly the set of nodes some decrement of this round takes from above k to k or below, and
+// of all the decrements a node receives exactly one does that (integer atomicSub returns the value before).  The thread
+// that sees old > k >= old - c appends the node to the next round's list and writes its core, onion layer and state
+// there and then.  Only when that list comes out empty (k must jump) do two sweeps over all n nodes run: kc_min (the
+// chip-wide minimum degree of the alive nodes: a wavefront reduction, one integer atomicMin per workgroup) and
+// kc_collect (F by the new k, appended one atomic per wavefront).
+// Bound: 2 (distinct core values) sweeps of 8 n bytes, plus one visit of every arc from each of its ends over the
+// whole run (a 4-byte gather of the other end's state; an atomicSub only when that end is still alive: about one per
+// edge), plus the hub pulls below.  Never rounds x n.
+//
+// Hubs (the CSR's hub list: rows longer than GRX_HUB_FACTOR * lanes_per_row) get a workgroup per row and round, on
+// both sides of the peel:
+//   * a hub in F walks its long row with all 256 threads;
+//   * a hub that stays alive PULLS its decrement: its workgroup counts the entries of its row that are in F (state ==
+//     layer) and subtracts the count once.  The threads that peel a neighbour of it read the hub flag in its state word
+//     and send nothing.  Chosen over collecting pushes in LDS because it needs no per-workgroup table and no key
+//     lookup per arc (the pusher reads the target's state word anyway, to skip the ends that have left), and because it
+//     puts one atomic on a hub's counter per round whatever the graph: the 1 500 leaves of a star that leave in one
+//     round send 0 decrements to the centre instead of 1 500.  Its price is that every alive hub row is read in every
+//     round: rounds x (arcs of the alive hub rows) coalesced column reads and 4-byte state gathers.
+//   For a directed graph a node's out-row and in-row are pulled separately (by the out CSR's and the in CSR's hub
+//   list); the two counts add up, and a reciprocal pair counts twice as in networkx's all_neighbors.
+//
+// State word of a node: > 0 = the round it left in (its onion layer); <= 0 = alive, minus the hub bits (1 = listed in
+// the out CSR's hub list, 2 = in the in CSR's; both for an undirected graph).  A decrement that reaches a node after
+// its crossing decrement (or after it left) changes nothing that is read again.  Appends go through an LDS buffer per
+// workgroup: one global atomic per workgroup and round on the list counter.
+// A one-thread finalize subtracts |F| from the alive count, advances `layer` or sets `done`, and raises the sweep flag
+// when the next list is empty; every launch returns at once after `done`, so the host enqueues KC_ROUND_BATCH rounds
+// between read-backs of (done, layer).  Integer arithmetic only; core and onion are the same in every run (the order
+// of the lists is not, and is never visible).  The CSRs must hold no self-loop (the caller's precondition).
+#include "grx_common.h"
+
+#include <algorithm>
+#include <climits>
+
+namespace {
+
+constexpr int KC_BLOCK = 256;
+constexpr int KC_GROUP = 8;                                  // lanes per frontier node in kc_peel_kernel
+constexpr int KC_ROUND_BATCH = 16;                           // rounds enqueued between two read-backs
+constexpr int KC_MAX_BLOCKS = 2048;
+constexpr int KC_APPEND_CAP = 2048;                          // LDS append buffer of a workgroup (entries)
+constexpr int KC_OUT_HUB = 1, KC_IN_HUB = 2;
+
+enum { KT_DONE = 0, KT_LAYER, KT_K, KT_MIN, KT_SWEEP, KT_ALIVE, KT_CNT0, KT_CNT1, KT_WORDS };
+
+size_t ws_bytes(int64_t n)
+{
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    return 4 * grx_align_up(nn * 4, 256) + 256;
+}
+
+struct KcState {
+    int32_t *deg, *state, *list0, *list1;
+    int32_t *ctrl;
+    int64_t *core, *onion;                                   // onion may be null
+};
+
+KcState carve(void *base, int64_t n, int64_t *core, int64_t *onion)
+{
+    const size_t nn = (size_t)(n > 0 ? n : 1), step = grx_align_up(nn * 4, 256);
+    char *p = reinterpret_cast<char *>(base);
+    KcState s;
+    s.deg = reinterpret_cast<int32_t *>(p); p += step;
+    s.state = reinterpret_cast<int32_t *>(p); p += step;
+    s.list0 = reinterpret_cast<int32_t *>(p); p += step;
+    s.list1 = reinterpret_cast<int32_t *>(p); p += step;
+    s.ctrl = reinterpret_cast<int32_t *>(p);
+    s.core = core;
+    s.onion = onion;
+    return s;
+}
+
+// what a round's kernels read from ctrl: the list of this round (F) and the one they append to
+struct KcRound {
+    int layer, kk, count;
+    const int32_t *cur;
+    int32_t *next, *next_count;
+};
+
+__device__ __forceinline__ KcRound round_of(const KcState &s)
+{
+    KcRound r;
+    r.layer = s.ctrl[KT_LAYER];
+    r.kk = s.ctrl[KT_SWEEP] ? max(s.ctrl[KT_K], s.ctrl[KT_MIN]) : s.ctrl[KT_K];
+    const int odd = r.layer & 1;
+    r.count = s.ctrl[KT_CNT0 + odd];
+    r.cur = odd ? s.list1 : s.list0;
+    r.next = odd ? s.list0 : s.list1;
+    r.next_count = &s.ctrl[KT_CNT0 + (odd ^ 1)];
+    return r;
+}
+
+// deg(u) -= c; the one decrement that takes u from above k to k or below puts u into the next round's F
+__device__ __forceinline__ void drop(int32_t u, int c, const KcRound &r, const KcState &s, int32_t *buf, int *bcount)
+{
+    const int old = atomicSub(&s.deg[u], c);
+    if (old > r.kk && old - c <= r.kk) {
+        s.state[u] = r.layer + 1;
+        s.core[u] = r.kk;
+        if (s.onion) s.onion[u] = r.layer + 1;
+        const int slot = atomicAdd(bcount, 1);
+        if (slot < KC_APPEND_CAP) buf[slot] = u;
+        else r.next[atomicAdd(r.next_count, 1)] = u;
+    }
+}
+
+// a node of F tells the other end u of one arc -- unless u left in this or an earlier round, or is an alive hub of
+// the CSR that holds the arc on u's side (`skip`: u's workgroup pulls it)
+__device__ __forceinline__ void push_arc(int32_t u, int skip, const KcRound &r, const KcState &s, int32_t *buf,
+                                         int *bcount)
+{
+    const int32_t su = s.state[u];
+    if (su > 0 ? su <= r.layer : ((-su) & skip) != 0) return;
+    drop(u, 1, r, s, buf, bcount);
+}
+
+// the workgroup's buffered appends, one atomic on the list counter; every thread of the workgroup calls it
+__device__ __forceinline__ void flush_appends(const KcRound &r, const int32_t *buf, const int *bcount, int *base)
+{
+    __syncthreads();
+    const int c = min(*bcount, KC_APPEND_CAP);
+    if (threadIdx.x == 0 && c) *base = atomicAdd(r.next_count, c);
+    __syncthreads();
+    for (int i = threadIdx.x; i < c; i += KC_BLOCK) r.next[*base + i] = buf[i];
+}
+
+__global__ __launch_bounds__(KC_BLOCK) void kc_init_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+                                                           const int64_t *__restrict__ in_row_ptr, KcState s)
+{
+    for (int64_t v = (int64_t)blockIdx.x * KC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * KC_BLOCK) {
+        int64_t d = row_ptr[v + 1] - row_ptr[v];
+        if (in_row_ptr) d += in_row_ptr[v + 1] - in_row_ptr[v];
+        s.deg[v] = (int32_t)d;
+        s.state[v] = 0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        s.ctrl[KT_DONE] = 0; s.ctrl[KT_LAYER] = 1; s.ctrl[KT_K] = 0; s.ctrl[KT_MIN] = INT_MAX;
+        s.ctrl[KT_SWEEP] = 1; s.ctrl[KT_ALIVE] = (int32_t)n; s.ctrl[KT_CNT0] = 0; s.ctrl[KT_CNT1] = 0;
+    }
+}
+
+// the hub bits of the state words (every listed row once per list: no two threads of a launch share a word)
+__global__ __launch_bounds__(KC_BLOCK) void kc_hub_flag_kernel(int64_t n, const int32_t *__restrict__ hub_rows,
+                                                               int64_t n_hub_rows, int bits, int32_t *__restrict__ state)
+{
+    const int64_t i = (int64_t)blockIdx.x * KC_BLOCK + threadIdx.x;
+    if (i >= n_hub_rows) return;
+    const int64_t h = hub_rows[i];
+    if (h < 0 || h >= n) return;                             // an id outside [0, n) is never written through
+    state[h] = -((-state[h]) | bits);
+}
+
+// sweep 1 (only when the list is empty): min deg over the alive nodes
+__global__ __launch_bounds__(KC_BLOCK) void kc_min_kernel(int64_t n, KcState s)
+{
+    __shared__ int smin;
+    if (s.ctrl[KT_DONE] || !s.ctrl[KT_SWEEP]) return;
+    if (threadIdx.x == 0) smin = INT_MAX;
+    __syncthreads();
+    int m = INT_MAX;
+    for (int64_t v = (int64_t)blockIdx.x * KC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * KC_BLOCK)
+        if (s.state[v] <= 0) m = min(m, s.deg[v]);
+#pragma unroll
+    for (int off = GRX_WAVE / 2; off > 0; off >>= 1) m = min(m, __shfl_xor(m, off, GRX_WAVE));
+    if (threadIdx.x % GRX_WAVE == 0 && m < INT_MAX) atomicMin(&smin, m);
+    __syncthreads();
+    if (threadIdx.x == 0 && smin < INT_MAX) atomicMin(&s.ctrl[KT_MIN], smin);
+}
+
+// sweep 2: F = the alive nodes with deg <= max(k, min), appended one atomic per wavefront
+__global__ __launch_bounds__(KC_BLOCK) void kc_collect_kernel(int64_t n, KcState s)
+{
+    if (s.ctrl[KT_DONE] || !s.ctrl[KT_SWEEP]) return;
+    const int layer = s.ctrl[KT_LAYER];
+    const int kk = max(s.ctrl[KT_K], s.ctrl[KT_MIN]);
+    int32_t *cur = (layer & 1) ? s.list1 : s.list0;
+    int32_t *cur_count = &s.ctrl[KT_CNT0 + (layer & 1)];
+    const int lane = threadIdx.x % GRX_WAVE;
+    // the trip count is the same in every lane of the workgroup: the ballot sees every lane
+    for (int64_t first = (int64_t)blockIdx.x * KC_BLOCK; first < n; first += (int64_t)gridDim.x * KC_BLOCK) {
+        const int64_t v = first + threadIdx.x;
+        const bool leaves = v < n && s.state[v] <= 0 && s.deg[v] <= kk;
+        const unsigned long long m = __ballot(leaves);
+        if (!m) continue;
+        int base = 0;
+        if (lane == 0) base = atomicAdd(cur_count, __popcll(m));
+        base = __shfl(base, 0, GRX_WAVE);
+        if (leaves) {
+            cur[base + __popcll(m & ((1ull << lane) - 1))] = (int32_t)v;
+            s.state[v] = layer;
+            s.core[v] = kk;
+            if (s.onion) s.onion[v] = layer;
+        }
+    }
+}
+
+// the peel of the rows up to hub_degree arcs: KC_GROUP lanes per node of F, over the list
+__global__ __launch_bounds__(KC_BLOCK) void kc_peel_kernel(const int64_t *__restrict__ row_ptr,
+                                                           const int32_t *__restrict__ col, int64_t hub_degree,
+                                                           const int64_t *__restrict__ in_row_ptr,
+                                                           const int32_t *__restrict__ in_col, int64_t in_hub_degree,
+                                                           KcState s)
+{
+    __shared__ int32_t buf[KC_APPEND_CAP];
+    __shared__ int bcount, base;
+    if (s.ctrl[KT_DONE]) return;
+    const KcRound r = round_of(s);
+    if (threadIdx.x == 0) bcount = 0;
+    __syncthreads();
+    constexpr int NODES = KC_BLOCK / KC_GROUP;
+    const int g = threadIdx.x % KC_GROUP;
+    for (int64_t i = (int64_t)blockIdx.x * NODES + threadIdx.x / KC_GROUP; i < r.count;
+         i += (int64_t)gridDim.x * NODES) {
+        const int64_t v = r.cur[i];
+        const int64_t b = row_ptr[v], e = row_ptr[v + 1];
+        if (e - b <= hub_degree)                              // longer rows: kc_hub_kernel
+            for (int64_t j = b + g; j < e; j += KC_GROUP) push_arc(col[j], KC_IN_HUB, r, s, buf, &bcount);
+        if (in_row_ptr) {
+            const int64_t ib = in_row_ptr[v], ie = in_row_ptr[v + 1];
+            if (ie - ib <= in_hub_degree)
+                for (int64_t j = ib + g; j < ie; j += KC_GROUP) push_arc(in_col[j], KC_OUT_HUB, r, s, buf, &bcount);
+        }
+    }
+    flush_appends(r, buf, &bcount, &base);
+}
+
+// one workgroup per hub row of one CSR: a hub in F pushes along its row; a hub that stays alive pulls -- counts the
+// entries of its row that are in F -- and subtracts once.  `skip`: the hub bit of the CSR that holds this CSR's arcs
+// on the other end's side (the in CSR for the out CSR's rows and the other way round)
+__global__ __launch_bounds__(KC_BLOCK) void kc_hub_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+                                                          const int32_t *__restrict__ col,
+                                                          const int32_t *__restrict__ hub_rows, int skip, KcState s)
+{
+    __shared__ int32_t buf[KC_APPEND_CAP];
+    __shared__ int bcount, base, total, own;
+    if (s.ctrl[KT_DONE]) return;
+    const KcRound r = round_of(s);
+    const int t = threadIdx.x;
+    const int32_t v = hub_rows[blockIdx.x];
+    if (v < 0 || v >= n) return;                             // an id outside [0, n) is never read through
+    if (t == 0) { bcount = 0; total = 0; own = s.state[v]; }   // one read: every wavefront takes the same branch
+    __syncthreads();
+    const int sv = own;
+    const int64_t b = row_ptr[v], e = row_ptr[v + 1];
+    if (sv == r.layer) {
+        for (int64_t j = b + t; j < e; j += KC_BLOCK) push_arc(col[j], skip, r, s, buf, &bcount);
+    } else if (sv <= 0) {
+        int c = 0;
+        for (int64_t j = b + t; j < e; j += KC_BLOCK) c += s.state[col[j]] == r.layer;
+#pragma unroll
+        for (int off = GRX_WAVE / 2; off > 0; off >>= 1) c += __shfl_xor(c, off, GRX_WAVE);
+        if (t % GRX_WAVE == 0 && c) atomicAdd(&total, c);
+        __syncthreads();
+        if (t == 0 && total) drop(v, total, r, s, buf, &bcount);
+    }
+    flush_appends(r, buf, &bcount, &base);
+}
+
+// one thread: F has left; the next round, or done when nobody is alive.  An empty next list asks for the sweeps
+__global__ void kc_finalize_kernel(KcState s)
+{
+    int32_t *ctrl = s.ctrl;
+    if (ctrl[KT_DONE]) return;
+    const int odd = ctrl[KT_LAYER] & 1;
+    if (ctrl[KT_SWEEP]) ctrl[KT_K] = max(ctrl[KT_K], ctrl[KT_MIN]);
+    ctrl[KT_ALIVE] -= ctrl[KT_CNT0 + odd];
+    ctrl[KT_CNT0 + odd] = 0;
+    ctrl[KT_MIN] = INT_MAX;
+    if (ctrl[KT_ALIVE] <= 0) {
+        ctrl[KT_DONE] = 1;                                  // KT_LAYER stays: the number of rounds run
+        return;
+    }
+    ctrl[KT_SWEEP] = ctrl[KT_CNT0 + (odd ^ 1)] == 0;
+    ctrl[KT_LAYER] += 1;
+}
+
+struct PinnedCtrl {
+    int32_t *h = nullptr;
+    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
+};
+thread_local PinnedCtrl g_ctrl;
+
+int read_ctrl(const int32_t *d_ctrl, int32_t out[2], hipStream_t st)
+{
+    if (!g_ctrl.h) {
+        void *h = nullptr;
+        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
+        g_ctrl.h = reinterpret_cast<int32_t *>(h);
+    }
+    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, 8, st);
+    if (rc == GRX_OK) rc = grx_fetch_wait(st);
+    if (rc != GRX_OK) return rc;
+    out[0] = g_ctrl.h[KT_DONE];
+    out[1] = g_ctrl.h[KT_LAYER];
+    return GRX_OK;
+}
+
+unsigned grid_for(int64_t items, int per_block)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(items, per_block), KC_MAX_BLOCKS));
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t grx_core_numbers_workspace_bytes(int64_t n) { return ws_bytes(n); }
+
+int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                     int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+                     const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, int64_t *d_core,
+                     int64_t *d_onion, int64_t *n_rounds, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_core_numbers: n = %lld out of range", (long long)n);
+    GRX_REQUIRE(d_row_ptr && d_col && d_core && d_workspace, "grx_core_numbers: null pointer");
+    GRX_REQUIRE(lanes_per_row >= 1, "grx_core_numbers: lanes_per_row must be >= 1");
+    GRX_REQUIRE(n_hub_rows >= 0 && n_hub_rows <= n && (n_hub_rows == 0 || d_hub_rows), "grx_core_numbers: hub list");
+    const bool directed = d_in_row_ptr != nullptr;
+    if (directed) {
+        GRX_REQUIRE(d_in_col, "grx_core_numbers: null pointer (in CSR)");
+        GRX_REQUIRE(in_lanes_per_row >= 1, "grx_core_numbers: in_lanes_per_row must be >= 1");
+        GRX_REQUIRE(n_in_hub_rows >= 0 && n_in_hub_rows <= n && (n_in_hub_rows == 0 || d_in_hub_rows),
+                    "grx_core_numbers: hub list (in CSR)");
+    } else {
+        GRX_REQUIRE(!d_in_col && !d_in_hub_rows && n_in_hub_rows == 0 && in_lanes_per_row == 0,
+                    "grx_core_numbers: the in CSR must be given whole or not at all");
+    }
+    GRX_REQUIRE(workspace_bytes >= ws_bytes(n), "grx_core_numbers: workspace %zu bytes, need %zu", workspace_bytes,
+                ws_bytes(n));
+    hipStream_t st = grx_stream(stream);
+    const KcState s = carve(d_workspace, n, d_core, d_onion);
+    const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
+    const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
+    const unsigned sweep_grid = grid_for(n, KC_BLOCK), peel_grid = grid_for(n, KC_BLOCK / KC_GROUP);
+
+    kc_init_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, d_row_ptr, d_in_row_ptr, s);
+    if (n_hub_rows)
+        kc_hub_flag_kernel<<<(unsigned)grx_ceil_div(n_hub_rows, KC_BLOCK), KC_BLOCK, 0, st>>>(
+            n, d_hub_rows, n_hub_rows, directed ? KC_OUT_HUB : KC_OUT_HUB | KC_IN_HUB, s.state);
+    if (n_in_hub_rows)
+        kc_hub_flag_kernel<<<(unsigned)grx_ceil_div(n_in_hub_rows, KC_BLOCK), KC_BLOCK, 0, st>>>(
+            n, d_in_hub_rows, n_in_hub_rows, KC_IN_HUB, s.state);
+    GRX_LAUNCH_CHECK();
+    int32_t h[2] = {0, 0};
+    int64_t issued = 0;
+    while (!h[0]) {
+        // every round but the last removes a node: at most n rounds
+        GRX_REQUIRE(issued <= n + 1, "grx_core_numbers: the peeling did not end after %lld rounds",
+                    (long long)issued);
+        for (int k = 0; k < KC_ROUND_BATCH; ++k, ++issued) {
+            kc_min_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, s);
+            kc_collect_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, s);
+            if (n_hub_rows)
+                kc_hub_kernel<<<(unsigned)n_hub_rows, KC_BLOCK, 0, st>>>(n, d_row_ptr, d_col, d_hub_rows, KC_IN_HUB,
+                                                                         s);
+            if (n_in_hub_rows)
+                kc_hub_kernel<<<(unsigned)n_in_hub_rows, KC_BLOCK, 0, st>>>(n, d_in_row_ptr, d_in_col, d_in_hub_rows,
+                                                                            KC_OUT_HUB, s);
+            kc_peel_kernel<<<peel_grid, KC_BLOCK, 0, st>>>(d_row_ptr, d_col, hub_degree, d_in_row_ptr, d_in_col,
+                                                           in_hub_degree, s);
+            kc_finalize_kernel<<<1, 1, 0, st>>>(s);
+            GRX_LAUNCH_CHECK();
+        }
+        const int rc = read_ctrl(s.ctrl, h, st);
+        if (rc != GRX_OK) return rc;
+    }
+    if (n_rounds) *n_rounds = h[1];
+    return GRX_OK;
+}
+
+}  // extern "C"

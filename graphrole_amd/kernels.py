@@ -1288,3 +1288,26 @@ def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor,
               csr.lanes_per_row, _ptr(count), _ptr(parent), _ptr(label), ctypes.byref(n_components), _ptr(ws), ws_bytes,
               _stream())
     return count, parent, label, int(n_components.value)
+
+
+def core_numbers(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR] = None,
+                 want_onion: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], int]:
+    """grx_core_numbers on the CSR of a graph's distinct arcs (no self-loops): (core int64[n], onion int64[n] = the
+    round every row is peeled in, n_rounds = the largest onion layer).  csr_in=None: an undirected graph, csr_out
+    symmetric; otherwise the in-adjacency of a directed graph (degree = in + out).  want_onion=False passes NULL for
+    onion (None then)."""
+    n = csr_out.n
+    lib = _lib.load()
+    ws_bytes = lib.grx_core_numbers_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    core = torch.empty(max(n, 1), dtype=torch.int64, device=device())
+    onion = torch.empty(max(n, 1), dtype=torch.int64, device=device()) if want_onion else None
+    if csr_in is None:
+        in_args = (None, None, None, 0, 0)
+    else:
+        in_args = (_ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.hub_rows), csr_in.n_hubs, csr_in.lanes_per_row)
+    n_rounds = ctypes.c_int64(0)
+    _lib.call('grx_core_numbers', n, _ptr(csr_out.row_ptr), _ptr(csr_out.col), _ptr(csr_out.hub_rows), csr_out.n_hubs,
+              csr_out.lanes_per_row, *in_args, _ptr(core), _ptr(onion), ctypes.byref(n_rounds), _ptr(ws), ws_bytes,
+              _stream())
+    return core, onion, int(n_rounds.value)

@@ -6,8 +6,9 @@ default arguments and is computed on the device CSR the feature extractor uses (
 triangle counts of grx_triangle_counts, PageRank and eigenvector centrality by the power iterations of
 csrc/grx_measures.hip, betweenness centrality (opt-in: O(n m)) by the batched Brandes passes of
 csrc/grx_betweenness.hip, and closeness and harmonic centrality (opt-in: O(n m)) from the per-target distance sums of
-the bitset multi-source BFS of csrc/grx_closeness.hip, and the number of biconnected components of every node (opt-in;
-more than one: an articulation point) by the Tarjan-Vishkin sweeps of csrc/grx_biconnected.hip.
+the bitset multi-source BFS of csrc/grx_closeness.hip, the number of biconnected components of every node (opt-in;
+more than one: an articulation point) by the Tarjan-Vishkin sweeps of csrc/grx_biconnected.hip, and the core number
+and onion layer of every node (opt-in) by the synchronous peeling of csrc/grx_kcore.hip.
 """
 from __future__ import annotations
 
@@ -35,12 +36,15 @@ CATALOGUE = {
     'closeness_centrality': 'nx.closeness_centrality(G, wf_improved=wf_improved)',
     'harmonic_centrality': 'nx.harmonic_centrality(G)',
     'biconnected_components': 'Counter(v for c in nx.biconnected_components(G) for v in c)',
+    'core_number': 'nx.core_number(G)',
+    'onion_layer': 'nx.onion_layers(G)',
 }
 
 #: catalogue entries computed only when named: not in ``available_measures`` nor in the default table -- the
-#: centralities because they cost O(n m), 'biconnected_components' (O(n + m) per sweep) because the default table and
-#: ``available_measures`` are pinned as they were before it existed
-OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality', 'biconnected_components')
+#: centralities because they cost O(n m), 'biconnected_components', 'core_number' and 'onion_layer' (O(n + m)) because
+#: the default table and ``available_measures`` are pinned as they were before they existed
+OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality', 'biconnected_components',
+          'core_number', 'onion_layer')
 
 
 def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
@@ -58,6 +62,10 @@ def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
         return f'networkx does not implement {CATALOGUE[name]} for a multigraph'
     if name == 'biconnected_components' and directed:
         return f'networkx does not implement nx.biconnected_components(G) for a {kind}'
+    if name in ('core_number', 'onion_layer') and multi:
+        return f'networkx does not implement {CATALOGUE[name]} for a multigraph'
+    if name == 'onion_layer' and directed:
+        return f'networkx does not implement nx.onion_layers(G) for a {kind}'
     return None
 
 
@@ -109,8 +117,9 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       ``.attrs['iterations']`` holds the power-iteration counts
     :raises ValueError: an unknown measure name
     :raises NotImplementedError: a measure that networkx does not implement for this kind of graph (among them
-      ``'biconnected_components'`` of a directed graph), or that is outside this implementation's scope (directed /
-      multigraph clustering and effective size)
+      ``'biconnected_components'`` and ``'onion_layer'`` of a directed graph, and ``'core_number'`` and
+      ``'onion_layer'`` of a multigraph or of a graph with a self-loop), or that is outside this implementation's scope
+      (directed / multigraph clustering and effective size)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
 
     Stated divergence: ``effective_size`` of a node whose only neighbour is itself is NaN (networkx raises
@@ -139,6 +148,9 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
                 raise NotImplementedError(why)
     if 'betweenness_centrality' in names:
         sources = _betweenness_sources(graph, k, seed)        # argument errors before any device work
+    peeled = [nm for nm in names if nm in ('core_number', 'onion_layer')]
+    if peeled:
+        _peeling_refusals(graph, peeled[0])                   # likewise: read from the host CSR
     K = graph._K()
     host, out, tr = graph._device_graph()
     loops = bool(graph._has_loops)
@@ -170,6 +182,16 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
         if 'blocks' not in cache:
             cache['blocks'] = K.biconnected(graph._structure_csrs()[0])
         return cache['blocks']
+
+    def peeling():
+        # one kernel call for both columns; the distinct arcs, out and (directed) in
+        if 'peeling' not in cache:
+            s_out, s_in = graph._structure_csrs()
+            if directed and s_in is None:
+                raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; '
+                                          f'core_number cannot be computed on it')
+            cache['peeling'] = K.core_numbers(s_out, s_in if directed else None, 'onion_layer' in names)
+        return cache['peeling']
 
     for nm in names:
         if nm == 'degree':
@@ -204,6 +226,10 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col, dt = distances()[2], np.dtype('float64')
         elif nm == 'biconnected_components':
             col, dt = blocks()[0], np.dtype('int64')
+        elif nm == 'core_number':
+            col, dt = peeling()[0], np.dtype('int64')
+        elif nm == 'onion_layer':
+            col, dt = peeling()[1], np.dtype('int64')
         elif nm == 'pagerank':
             col, iterations[nm] = K.pagerank(tr if directed else out, K.row_sums(out, False), alpha, tol, max_iter)
             dt = np.dtype('float64')
@@ -479,3 +505,46 @@ def biconnected_components(G) -> list:
     groups = np.split(members, cuts) if len(members) else []
     assert len(groups) == n_components
     return [set(g.tolist()) if plain else {labels[i] for i in g.tolist()} for g in groups]
+
+
+def _peeling_refusals(graph, name: str) -> None:
+    """networkx's own limits of core_number and onion_layers that the kind of graph does not show: a self-loop, and
+    parallel edges of an adapter without a multigraph flag.  Read from the host CSR and edge list: no device work."""
+    g = graph.to_csr()
+    if not getattr(graph, '_multi', False) and hasattr(graph, '_is_simple') and not graph._is_simple():
+        if graph.get_num_edges() != g.num_edges:
+            raise NotImplementedError(f'networkx does not implement {CATALOGUE[name]} for a multigraph')
+    if getattr(g, 'n_loops', 1) > 0:
+        raise NotImplementedError(f'networkx does not implement {CATALOGUE[name]} for a graph with self-loops; remove '
+                                  f'them first: G.remove_edges_from(nx.selfloop_edges(G))')
+
+
+def core_number(G) -> pd.Series:
+    """
+    The core number of every node on the GPU -- the largest k such that the node belongs to the k-core, the maximal
+    subgraph in which every node has degree at least k: ``nx.core_number(G)`` of networkx 3.4.2 (core.py), by the
+    synchronous peeling of csrc/grx_kcore.hip.  For a directed graph the degree is in + out, as in networkx.
+
+    :param G: any graph ``node_measures`` accepts, undirected or directed
+    :return: int64 Series named ``core_number`` indexed by the sorted node labels; equal to networkx
+    :raises NotImplementedError: G has a self-loop (networkx raises NetworkXNotImplemented there; remove them with
+      ``G.remove_edges_from(nx.selfloop_edges(G))``) or is a multigraph (networkx implements neither) -- networkx's
+      own limits, not divergences; or G is directed and its adapter has no in-adjacency
+    """
+    return node_measures(G, ['core_number'])['core_number']
+
+
+def onion_layers(G) -> pd.Series:
+    """
+    The onion layer of every node on the GPU -- the round of the peeling in which the node is removed, which refines
+    the core number (Hebert-Dufresne, Grochow and Allard, 2016): ``nx.onion_layers(G)`` of networkx 3.4.2 (core.py),
+    from the same kernel call as ``core_number``.  Name ``'core_number'`` and ``'onion_layer'`` in one
+    ``node_measures`` call to get both from one pass.
+
+    :param G: any undirected graph ``node_measures`` accepts
+    :return: int64 Series named ``onion_layer`` indexed by the sorted node labels (layers count from 1); equal to
+      networkx
+    :raises NotImplementedError: G is directed, has a self-loop or is a multigraph: networkx implements onion_layers
+      for none of them (its own limits, not divergences)
+    """
+    return node_measures(G, ['onion_layer'])['onion_layer']

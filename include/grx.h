@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define GRX_VERSION 1000         /* 0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
+#define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures)
+                                    0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
                                     measures)
@@ -906,6 +907,35 @@ size_t grx_biconnected_workspace_bytes(int64_t n);
 int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                     int64_t n_hub_rows, int lanes_per_row, int64_t *d_count, int32_t *d_parent, int32_t *d_label,
                     int64_t *n_components, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_core_numbers: the core number of every node -- networkx.core_number(G) (networkx/algorithms/core.py) -- and,
+ *   for an undirected graph, its onion layer -- networkx.onion_layers(G): the round in which the node is peeled -- by
+ *   synchronous peeling: k = max(k, min degree over the alive nodes); every alive node of degree <= k (degrees as at
+ *   the start of the round) gets core = k and onion = the round's number (from 1) and leaves; the degree of every
+ *   node at the other end of one of its arcs drops by one.
+ *   d_row_ptr / d_col: the CSR of the graph's distinct arcs, rows in any order.  All d_in_* NULL / 0: an undirected
+ *   graph, the CSR symmetric (every edge from both ends).  Otherwise a directed graph: the first CSR holds the
+ *   out-arcs, d_in_row_ptr / d_in_col the in-arcs (its transpose); degree = in + out, a leaving node decrements along
+ *   both, so a reciprocal pair counts twice (networkx's all_neighbors); d_onion is then the peeling round as well,
+ *   which networkx does not define.  PRECONDITION: no self-loop entry in either CSR (networkx raises
+ *   NetworkXNotImplemented for such a graph; the caller refuses it).  Weights are not read.  Rows longer than
+ *   GRX_HUB_FACTOR * lanes_per_row (in_lanes_per_row) must be listed in d_hub_rows (d_in_hub_rows).
+ *   Method: see the header of csrc/grx_kcore.hip.  The next round's nodes are collected in a list by the decrement
+ *   that takes a node's degree from above k to k or below; all n nodes are swept (twice) only when k jumps.  Cost: 2
+ *   sweeps per distinct core value, every arc visited once from each end over the whole run, and every alive hub row
+ *   read once per round (a hub pulls its decrement instead of taking one atomic per leaving neighbour).  16 rounds
+ *   are enqueued per read-back of (done, round).
+ *   d_core:  int64[n], overwritten.   d_onion: int64[n] or NULL.
+ *   n_rounds: HOST int64 or NULL: the number of rounds run = the largest onion layer.
+ *   Exact (integers only; the outputs do not depend on the order of the atomics): the same bits in every run.
+ *   n < 2^31.  d_workspace: grx_core_numbers_workspace_bytes(n) bytes (about 16 n).  The call waits for the stream.
+ */
+size_t grx_core_numbers_workspace_bytes(int64_t n);
+int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                     int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+                     const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, int64_t *d_core,
+                     int64_t *d_onion, int64_t *n_rounds, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
