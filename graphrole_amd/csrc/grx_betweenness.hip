@@ -11,9 +11,7 @@
 //
 // Forward, level l -> l + 1: pull over the IN-adjacency.  An unreached cell gets sigma = sum of sigma(u) over the
 //   in-neighbours u at level l (whole numbers below 2^53: exact in any order).  Rows settled in every lane of the
-//   chunk are skipped.  A one-thread finalize advances the device level or sets `done` when no lane reached a new
-//   node; every launch returns at once after `done`, so the host enqueues levels in batches and reads (done, depth)
-//   back once per batch.
+//   chunk are skipped.  The levels run as a device-steered round loop (grx_common.h); the level word ends as the depth.
 // Backward, level l = depth .. 1: pull over the OUT-adjacency.  delta(v) = sum over successors w at level l + 1 of
 //   sigma(v) * coeff(w), each term networkx's own product; then coeff(v) = (1 + delta(v)) / sigma(v) replaces sigma(v).
 // Accumulation: bc[v] adds the sources' contributions one after another in the caller's order (the sources of a
@@ -30,25 +28,24 @@
 
 namespace {
 
-constexpr int BC_BLOCK = 256;
-constexpr int BC_WAVES = BC_BLOCK / GRX_WAVE;
-constexpr int BC_MAX_BATCH = 256;
-constexpr int BC_LEVEL_BATCH = 8;                            // forward levels enqueued between two read-backs
-constexpr int BC_MAX_ROW_BLOCKS = 1024;
-constexpr size_t BC_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of B
+constexpr int BW_BLOCK = 256;
+constexpr int BW_WAVES = BW_BLOCK / GRX_WAVE;
+constexpr int BW_MAX_BATCH = 256;
+constexpr int BW_LEVEL_BATCH = 8;                            // forward levels enqueued between two read-backs
+constexpr int BW_MAX_ROW_BLOCKS = 1024;
+constexpr int BW_MAX_BLOCKS = 2048;                           // grid of the per-element launches
+constexpr size_t BW_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of B
 
-constexpr int32_t BC_IDLE = 0x7fffffff;
+constexpr int32_t BW_IDLE = 0x7fffffff;
 
-enum { CT_DONE = 0, CT_LEVEL, CT_FOUND, CT_COUNT };
-
-// B of batch = 0: the widest multiple of 64 up to 256 whose state fits BC_DEFAULT_STATE_BYTES (at least 64, so above
+// B of batch = 0: the widest multiple of 64 up to 256 whose state fits BW_DEFAULT_STATE_BYTES (at least 64, so above
 // ~3.35 M nodes the state is 20 n 64 bytes, more than the budget), and no wider than the source list
 int choose_batch(int64_t n, int batch, int64_t n_sources)
 {
     if (batch > 0) return batch;
     const size_t per_lane = (size_t)(n > 0 ? n : 1) * 20;   // level 4 + sigma 8 + delta 8 bytes per (node, source)
-    const int64_t b = (int64_t)(BC_DEFAULT_STATE_BYTES / per_lane) / GRX_WAVE * GRX_WAVE;
-    const int64_t widest = std::max<int64_t>(GRX_WAVE, std::min<int64_t>(b, BC_MAX_BATCH));
+    const int64_t b = (int64_t)(BW_DEFAULT_STATE_BYTES / per_lane) / GRX_WAVE * GRX_WAVE;
+    const int64_t widest = std::max<int64_t>(GRX_WAVE, std::min<int64_t>(b, BW_MAX_BATCH));
     const int64_t needed = std::max<int64_t>(GRX_WAVE, grx_ceil_div(n_sources, GRX_WAVE) * GRX_WAVE);
     return (int)std::min<int64_t>(widest, needed);
 }
@@ -59,17 +56,17 @@ size_t ws_bytes(int64_t n, int B)
     return grx_align_up(cells * 4, 256) + 2 * grx_align_up(cells * 8, 256) + grx_align_up((size_t)B * 4, 256) + 256;
 }
 
-struct BcWs {
+struct BwWs {
     int32_t *level;
     double *sigma, *delta;
     int32_t *reach, *ctrl;
 };
 
-BcWs carve(void *base, int64_t n, int B)
+BwWs carve(void *base, int64_t n, int B)
 {
     const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)B;
     char *p = reinterpret_cast<char *>(base);
-    BcWs w;
+    BwWs w;
     w.level = reinterpret_cast<int32_t *>(p); p += grx_align_up(cells * 4, 256);
     w.sigma = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
     w.delta = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
@@ -78,23 +75,17 @@ BcWs carve(void *base, int64_t n, int B)
     return w;
 }
 
-__global__ __launch_bounds__(BC_BLOCK) void bc_zero_kernel(int64_t n, double *__restrict__ bc)
-{
-    for (int64_t v = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BC_BLOCK)
-        bc[v] = 0.0;
-}
-
-// -1 (not reached) in the lanes of the batch's sources, BC_IDLE in the unused lanes of a last, partial batch (settled
+// -1 (not reached) in the lanes of the batch's sources, BW_IDLE in the unused lanes of a last, partial batch (settled
 // for the row skips, never equal to a level)
-__global__ __launch_bounds__(BC_BLOCK) void bc_level_init_kernel(int64_t cells, int B, int count,
+__global__ __launch_bounds__(BW_BLOCK) void bw_level_init_kernel(int64_t cells, int B, int count,
                                                                  int32_t *__restrict__ level)
 {
-    for (int64_t i = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; i < cells; i += (int64_t)gridDim.x * BC_BLOCK)
-        level[i] = (int)(i % B) < count ? -1 : BC_IDLE;
+    for (int64_t i = (int64_t)blockIdx.x * BW_BLOCK + threadIdx.x; i < cells; i += (int64_t)gridDim.x * BW_BLOCK)
+        level[i] = (int)(i % B) < count ? -1 : BW_IDLE;
 }
 
 // lane b < count: source s_b at level 0 with sigma 1 (networkx: sigma[s] = 1.0, D[s] = 0); reach = len(S) so far
-__global__ __launch_bounds__(BC_BLOCK) void bc_source_init_kernel(int64_t n, int B, int count,
+__global__ __launch_bounds__(BW_BLOCK) void bw_source_init_kernel(int64_t n, int B, int count,
                                                                   const int32_t *__restrict__ src,
                                                                   int32_t *__restrict__ level,
                                                                   double *__restrict__ sigma,
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_source_init_kernel(int64_t n, int
             sigma[cell] = 1.0;
         }
     }
-    if (b == 0) { ctrl[CT_DONE] = 0; ctrl[CT_LEVEL] = 0; ctrl[CT_FOUND] = 0; }
+    if (b == 0) { ctrl[GRX_CT_DONE] = 0; ctrl[GRX_CT_LEVEL] = 0; ctrl[GRX_CT_FOUND] = 0; }
 }
 
 // sigma(v) of one lane pulled over arcs [b, e) with stride `step` (in-neighbours u at level l); whole numbers
@@ -169,25 +160,25 @@ __device__ __forceinline__ double pull_delta(int64_t b, int64_t e, int step, con
 }
 
 // forward, rows up to hub_degree arcs: one wavefront per (row, chunk blockIdx.y)
-__global__ __launch_bounds__(BC_BLOCK) void bc_forward_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(BW_BLOCK) void bw_forward_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
                                                               const int32_t *__restrict__ col, int64_t hub_degree,
                                                               int B, int32_t *__restrict__ level,
                                                               double *__restrict__ sigma,
                                                               int32_t *__restrict__ reach,
                                                               int32_t *__restrict__ ctrl)
 {
-    if (ctrl[CT_DONE]) return;
-    const int l = ctrl[CT_LEVEL];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL];
     const int lane = threadIdx.x % GRX_WAVE;
     const int off = blockIdx.y * GRX_WAVE + lane;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / GRX_WAVE);
     int found = 0;
-    for (int64_t v = (int64_t)blockIdx.x * BC_WAVES + wave; v < n; v += (int64_t)gridDim.x * BC_WAVES) {
+    for (int64_t v = (int64_t)blockIdx.x * BW_WAVES + wave; v < n; v += (int64_t)gridDim.x * BW_WAVES) {
         const int64_t cell = v * B + off;
         const bool open = level[cell] < 0;
         if (!__ballot(open)) continue;                      // settled in every lane of the chunk
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-        if (e - b > hub_degree) continue;                   // bc_forward_hub_kernel
+        if (e - b > hub_degree) continue;                   // bw_forward_hub_kernel
         const double acc = pull_sigma(b, e, 1, col, level, sigma, B, off, l);
         if (open && acc != 0.0) {
             level[cell] = l + 1;
@@ -196,11 +187,11 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_forward_kernel(int64_t n, const i
         }
     }
     if (found) atomicAdd(&reach[off], found);
-    if (__ballot(found != 0) && lane == 0) ctrl[CT_FOUND] = 1;
+    if (__ballot(found != 0) && lane == 0) ctrl[GRX_CT_FOUND] = 1;
 }
 
 // forward, hub rows: one workgroup per (hub row, chunk); the four wavefronts take every fourth arc
-__global__ __launch_bounds__(BC_BLOCK) void bc_forward_hub_kernel(const int64_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(BW_BLOCK) void bw_forward_hub_kernel(const int64_t *__restrict__ row_ptr,
                                                                   const int32_t *__restrict__ col,
                                                                   const int32_t *__restrict__ hub_rows, int B,
                                                                   int32_t *__restrict__ level,
@@ -208,9 +199,9 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_forward_hub_kernel(const int64_t 
                                                                   int32_t *__restrict__ reach,
                                                                   int32_t *__restrict__ ctrl)
 {
-    __shared__ double part[BC_WAVES][GRX_WAVE];
-    if (ctrl[CT_DONE]) return;
-    const int l = ctrl[CT_LEVEL];
+    __shared__ double part[BW_WAVES][GRX_WAVE];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL];
     const int lane = threadIdx.x % GRX_WAVE, wave = threadIdx.x / GRX_WAVE;
     const int off = blockIdx.y * GRX_WAVE + lane;
     const int64_t v = hub_rows[blockIdx.x];
@@ -218,7 +209,7 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_forward_hub_kernel(const int64_t 
     const bool open = level[cell] < 0;
     if (!__ballot(open)) return;                            // the same in every wavefront of the workgroup
     const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-    part[wave][lane] = pull_sigma(b + wave, e, BC_WAVES, col, level, sigma, B, off, l);
+    part[wave][lane] = pull_sigma(b + wave, e, BW_WAVES, col, level, sigma, B, off, l);
     __syncthreads();
     if (wave != 0) return;
     const double acc = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
@@ -228,19 +219,7 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_forward_hub_kernel(const int64_t 
         sigma[cell] = acc;
         atomicAdd(&reach[off], 1);
     }
-    if (__ballot(hit) && lane == 0) ctrl[CT_FOUND] = 1;
-}
-
-// one thread: next level, or done when level l reached nothing new (then ctrl[CT_LEVEL] = depth)
-__global__ void bc_forward_finalize_kernel(int32_t *__restrict__ ctrl)
-{
-    if (ctrl[CT_DONE]) return;
-    if (ctrl[CT_FOUND]) {
-        ctrl[CT_LEVEL] += 1;
-        ctrl[CT_FOUND] = 0;
-    } else {
-        ctrl[CT_DONE] = 1;
-    }
+    if (__ballot(hit) && lane == 0) ctrl[GRX_CT_FOUND] = 1;
 }
 
 // networkx _accumulate_*: coeff = (1 + delta[w]) / sigma[w]; delta[v] += sigma[v] * coeff
@@ -252,7 +231,7 @@ __device__ __forceinline__ void settle(int64_t cell, double d, double sv, double
 }
 
 // backward, level l: cells at level l pull delta from their successors at l + 1; one wavefront per (row, chunk)
-__global__ __launch_bounds__(BC_BLOCK) void bc_backward_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(BW_BLOCK) void bw_backward_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
                                                                const int32_t *__restrict__ col, int64_t hub_degree,
                                                                int B, int l, const int32_t *__restrict__ level,
                                                                double *__restrict__ sigma,
@@ -261,26 +240,26 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_backward_kernel(int64_t n, const 
     const int lane = threadIdx.x % GRX_WAVE;
     const int off = blockIdx.y * GRX_WAVE + lane;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / GRX_WAVE);
-    for (int64_t v = (int64_t)blockIdx.x * BC_WAVES + wave; v < n; v += (int64_t)gridDim.x * BC_WAVES) {
+    for (int64_t v = (int64_t)blockIdx.x * BW_WAVES + wave; v < n; v += (int64_t)gridDim.x * BW_WAVES) {
         const int64_t cell = v * B + off;
         const bool mine = level[cell] == l;
         if (!__ballot(mine)) continue;
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-        if (e - b > hub_degree) continue;                   // bc_backward_hub_kernel
+        if (e - b > hub_degree) continue;                   // bw_backward_hub_kernel
         const double sv = mine ? sigma[cell] : 1.0;
         const double d = pull_delta(b, e, 1, col, level, sigma, B, off, l + 1, sv);
         if (mine) settle(cell, d, sv, sigma, delta);
     }
 }
 
-__global__ __launch_bounds__(BC_BLOCK) void bc_backward_hub_kernel(const int64_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(BW_BLOCK) void bw_backward_hub_kernel(const int64_t *__restrict__ row_ptr,
                                                                    const int32_t *__restrict__ col,
                                                                    const int32_t *__restrict__ hub_rows, int B, int l,
                                                                    const int32_t *__restrict__ level,
                                                                    double *__restrict__ sigma,
                                                                    double *__restrict__ delta)
 {
-    __shared__ double part[BC_WAVES][GRX_WAVE];
+    __shared__ double part[BW_WAVES][GRX_WAVE];
     const int lane = threadIdx.x % GRX_WAVE, wave = threadIdx.x / GRX_WAVE;
     const int off = blockIdx.y * GRX_WAVE + lane;
     const int64_t v = hub_rows[blockIdx.x];
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_backward_hub_kernel(const int64_t
     if (!__ballot(mine)) return;
     const int64_t b = row_ptr[v], e = row_ptr[v + 1];
     const double sv = mine ? sigma[cell] : 1.0;
-    part[wave][lane] = pull_delta(b + wave, e, BC_WAVES, col, level, sigma, B, off, l + 1, sv);
+    part[wave][lane] = pull_delta(b + wave, e, BW_WAVES, col, level, sigma, B, off, l + 1, sv);
     __syncthreads();
     if (wave != 0 || !mine) return;
     settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, sigma, delta);
@@ -297,55 +276,29 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_backward_hub_kernel(const int64_t
 
 // bc[v] += the contributions of the batch's sources in lane order (networkx: betweenness[w] += delta[w] for w != s;
 // with endpoints betweenness[s] += len(S) - 1 and betweenness[w] += delta[w] + 1)
-__global__ __launch_bounds__(BC_BLOCK) void bc_accumulate_kernel(int64_t n, int B, int count, int endpoints,
+__global__ __launch_bounds__(BW_BLOCK) void bw_accumulate_kernel(int64_t n, int B, int count, int endpoints,
                                                                  const int32_t *__restrict__ level,
                                                                  const double *__restrict__ delta,
                                                                  const int32_t *__restrict__ reach,
                                                                  double *__restrict__ bc)
 {
-    for (int64_t v = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BC_BLOCK) {
+    for (int64_t v = (int64_t)blockIdx.x * BW_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BW_BLOCK) {
         const int32_t *lv = level + v * B;
         const double *dv = delta + v * B;
         double acc = bc[v];
         for (int b = 0; b < count; ++b) {
             const int l = lv[b];
-            if (l > 0 && l != BC_IDLE) acc += endpoints ? dv[b] + 1.0 : dv[b];
+            if (l > 0 && l != BW_IDLE) acc += endpoints ? dv[b] + 1.0 : dv[b];
             else if (l == 0 && endpoints) acc += (double)(reach[b] - 1);
         }
         bc[v] = acc;
     }
 }
 
-__global__ __launch_bounds__(BC_BLOCK) void bc_scale_kernel(int64_t n, double scale, double *__restrict__ bc)
+__global__ __launch_bounds__(BW_BLOCK) void bw_scale_kernel(int64_t n, double scale, double *__restrict__ bc)
 {
-    for (int64_t v = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BC_BLOCK)
+    for (int64_t v = (int64_t)blockIdx.x * BW_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BW_BLOCK)
         bc[v] *= scale;
-}
-
-struct PinnedCtrl {
-    int32_t *h = nullptr;
-    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
-};
-thread_local PinnedCtrl g_ctrl;
-
-int read_ctrl(const int32_t *d_ctrl, int32_t out[2], hipStream_t st)
-{
-    if (!g_ctrl.h) {
-        void *h = nullptr;
-        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
-        g_ctrl.h = reinterpret_cast<int32_t *>(h);
-    }
-    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, 8, st);
-    if (rc == GRX_OK) rc = grx_fetch_wait(st);
-    if (rc != GRX_OK) return rc;
-    out[0] = g_ctrl.h[CT_DONE];
-    out[1] = g_ctrl.h[CT_LEVEL];
-    return GRX_OK;
-}
-
-int elem_grid(int64_t n)
-{
-    return (int)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(n, BC_BLOCK), 2048));
 }
 
 }  // namespace
@@ -366,8 +319,8 @@ int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
     GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_betweenness: n = %lld out of range", (long long)n);
     GRX_REQUIRE(d_row_ptr && d_col && d_bc && d_workspace, "grx_betweenness: null pointer");
     GRX_REQUIRE(n_sources >= 0 && (n_sources == 0 || d_sources), "grx_betweenness: source list");
-    GRX_REQUIRE(batch == 0 || (batch > 0 && batch <= BC_MAX_BATCH && batch % GRX_WAVE == 0),
-                "grx_betweenness: batch must be 0 or a multiple of 64 up to %d (got %d)", BC_MAX_BATCH, batch);
+    GRX_REQUIRE(batch == 0 || (batch > 0 && batch <= BW_MAX_BATCH && batch % GRX_WAVE == 0),
+                "grx_betweenness: batch must be 0 or a multiple of 64 up to %d (got %d)", BW_MAX_BATCH, batch);
     const bool directed = d_in_row_ptr != nullptr;
     GRX_REQUIRE(!directed || d_in_col, "grx_betweenness: d_in_col is required with d_in_row_ptr");
     if (!directed) {                                         // undirected: the CSR is its own in-adjacency
@@ -383,55 +336,48 @@ int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
     GRX_REQUIRE(workspace_bytes >= ws_bytes(n, B), "grx_betweenness: workspace %zu bytes, need %zu", workspace_bytes,
                 ws_bytes(n, B));
     hipStream_t st = grx_stream(stream);
-    const BcWs ws = carve(d_workspace, n, B);
+    const BwWs ws = carve(d_workspace, n, B);
     const int chunks = B / GRX_WAVE;
-    const int egrid = elem_grid(n);
-    const dim3 row_grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(n, BC_WAVES),
-                                                                          BC_MAX_ROW_BLOCKS)),
-                        (unsigned)chunks);
+    const unsigned egrid = grx_grid(n, BW_BLOCK, BW_MAX_BLOCKS);
+    const dim3 row_grid(grx_grid(n, BW_WAVES, BW_MAX_ROW_BLOCKS), (unsigned)chunks);
     const int64_t out_hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
     const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
     const int64_t cells = n * (int64_t)B;
     const int64_t *in_rp = directed ? d_in_row_ptr : d_row_ptr;
 
-    bc_zero_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, d_bc);
+    grx_fill64(reinterpret_cast<uint64_t *>(d_bc), n, 0, st);
     GRX_LAUNCH_CHECK();
     for (int64_t first = 0; first < n_sources; first += B) {
         const int count = (int)std::min<int64_t>(B, n_sources - first);
-        bc_level_init_kernel<<<elem_grid(cells), BC_BLOCK, 0, st>>>(cells, B, count, ws.level);
-        bc_source_init_kernel<<<1, BC_MAX_BATCH, 0, st>>>(n, B, count, d_sources + first, ws.level, ws.sigma, ws.reach,
+        bw_level_init_kernel<<<grx_grid(cells, BW_BLOCK, BW_MAX_BLOCKS), BW_BLOCK, 0, st>>>(cells, B, count, ws.level);
+        bw_source_init_kernel<<<1, BW_MAX_BATCH, 0, st>>>(n, B, count, d_sources + first, ws.level, ws.sigma, ws.reach,
                                                           ws.ctrl);
         GRX_LAUNCH_CHECK();
-        int32_t h[2] = {0, 0};
-        int64_t issued = 0;
-        while (!h[0]) {
-            // a BFS has at most n levels; one more launch finds the empty frontier
-            GRX_REQUIRE(issued <= n + 1, "grx_betweenness: the forward pass did not end after %lld levels",
-                        (long long)issued);
-            for (int k = 0; k < BC_LEVEL_BATCH; ++k, ++issued) {
+        int32_t h[2];
+        // a BFS has at most n levels; one more launch finds the empty frontier
+        const int rc = grx_run_rounds(
+            "grx_betweenness: the forward pass did not end after %lld levels", BW_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st,
+            [&] {
                 if (n_in_hub_rows)
-                    bc_forward_hub_kernel<<<dim3((unsigned)n_in_hub_rows, (unsigned)chunks), BC_BLOCK, 0, st>>>(
+                    bw_forward_hub_kernel<<<dim3((unsigned)n_in_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
                         in_rp, d_in_col, d_in_hub_rows, B, ws.level, ws.sigma, ws.reach, ws.ctrl);
-                bc_forward_kernel<<<row_grid, BC_BLOCK, 0, st>>>(n, in_rp, d_in_col, in_hub_degree, B, ws.level,
+                bw_forward_kernel<<<row_grid, BW_BLOCK, 0, st>>>(n, in_rp, d_in_col, in_hub_degree, B, ws.level,
                                                                  ws.sigma, ws.reach, ws.ctrl);
-                bc_forward_finalize_kernel<<<1, 1, 0, st>>>(ws.ctrl);
-                GRX_LAUNCH_CHECK();
-            }
-            const int rc = read_ctrl(ws.ctrl, h, st);
-            if (rc != GRX_OK) return rc;
-        }
-        for (int l = h[1]; l >= 1; --l) {                   // deepest level first; the sources need no delta
+                return grx_frontier_advance(ws.ctrl, st);
+            });
+        if (rc != GRX_OK) return rc;
+        for (int l = h[GRX_CT_LEVEL]; l >= 1; --l) {        // deepest level first; the sources need no delta
             if (n_hub_rows)
-                bc_backward_hub_kernel<<<dim3((unsigned)n_hub_rows, (unsigned)chunks), BC_BLOCK, 0, st>>>(
+                bw_backward_hub_kernel<<<dim3((unsigned)n_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
                     d_row_ptr, d_col, d_hub_rows, B, l, ws.level, ws.sigma, ws.delta);
-            bc_backward_kernel<<<row_grid, BC_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, l, ws.level,
+            bw_backward_kernel<<<row_grid, BW_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, l, ws.level,
                                                               ws.sigma, ws.delta);
             GRX_LAUNCH_CHECK();
         }
-        bc_accumulate_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, B, count, endpoints, ws.level, ws.delta, ws.reach, d_bc);
+        bw_accumulate_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, B, count, endpoints, ws.level, ws.delta, ws.reach, d_bc);
         GRX_LAUNCH_CHECK();
     }
-    bc_scale_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, scale, d_bc);
+    bw_scale_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, scale, d_bc);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }

@@ -26,8 +26,8 @@
 //     count[top] += 1 per component, and every non-root adds 1 for its own parent edge.
 //
 // Steps 2 to 5 are one launch (two with hub rows) per BFS level; each sweep is O(n + m) work (the BFS reads every
-// level[] once per level on top: O(D n)).  The BFS enqueues its levels in batches and reads (done, level) back once
-// per batch.  A deep graph (a path) is bound by launch latency, D launches per sweep; that case is not optimised.
+// level[] once per level on top: O(D n)).  The BFS levels run as a device-steered round loop (grx_common.h).  A deep
+// graph (a path) is bound by launch latency, D launches per sweep; that case is not optimised.
 // int32 ids, integer vector atomics only, no floating point.
 #include "grx_common.h"
 
@@ -45,7 +45,7 @@ constexpr int BC_SCAN_ITEMS = 8;
 constexpr int BC_SCAN_TILE = BC_BLOCK * BC_SCAN_ITEMS;
 constexpr int BC_BINS = 1024;                                // levels counted in LDS first; deeper ones straight in HBM
 
-enum { CT_DONE = 0, CT_LEVEL, CT_FOUND, CT_NCOMP, CT_COUNT };
+enum { CT_NCOMP = GRX_CT_BFS_WORDS, CT_COUNT };   // after the three words of the BFS loop
 
 size_t array_bytes(int64_t n) { return grx_align_up(((size_t)(n > 0 ? n : 1) + 2) * sizeof(int32_t), 256); }
 
@@ -137,11 +137,6 @@ __device__ __forceinline__ int block_excl_scan(int x, int *total, int *lds)
 
 #define BC_FOR_EACH(v, n) \
     for (int64_t v = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; v < (n); v += (int64_t)gridDim.x * BC_BLOCK)
-
-__global__ __launch_bounds__(BC_BLOCK) void bc_fill_kernel(int64_t count, int32_t *__restrict__ a, int value)
-{
-    BC_FOR_EACH(i, count) a[i] = value;
-}
 
 __global__ __launch_bounds__(BC_BLOCK) void bc_iota_kernel(int64_t n, int32_t *__restrict__ a)
 {
@@ -266,15 +261,15 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_bfs_kernel(int64_t n, const int64
                                                           const int32_t *__restrict__ col, int64_t hub_degree,
                                                           int32_t *level, int32_t *parent, int32_t *ctrl)
 {
-    if (ctrl[CT_DONE]) return;
-    const int l = ctrl[CT_LEVEL];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL];
     bool found = false;
     BC_FOR_EACH(v, n) {
         if (ld(level + v) != l) continue;
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
         if (e - b <= hub_degree) found |= bfs_row((int)v, l, b, e, 1, col, level, parent);
     }
-    if (found) st(ctrl + CT_FOUND, 1);
+    if (found) st(ctrl + GRX_CT_FOUND, 1);
 }
 
 __global__ __launch_bounds__(BC_BLOCK) void bc_bfs_hub_kernel(const int64_t *__restrict__ row_ptr,
@@ -282,23 +277,11 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_bfs_hub_kernel(const int64_t *__r
                                                               const int32_t *__restrict__ hub_rows, int32_t *level,
                                                               int32_t *parent, int32_t *ctrl)
 {
-    if (ctrl[CT_DONE]) return;
-    const int l = ctrl[CT_LEVEL];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL];
     const int v = hub_rows[blockIdx.x];
     if (ld(level + v) != l) return;
-    if (bfs_row(v, l, row_ptr[v] + threadIdx.x, row_ptr[v + 1], BC_BLOCK, col, level, parent)) st(ctrl + CT_FOUND, 1);
-}
-
-// one thread: next level, or done when this level reached nothing new (CT_LEVEL stays the deepest level)
-__global__ void bc_bfs_finalize_kernel(int32_t *__restrict__ ctrl)
-{
-    if (ctrl[CT_DONE]) return;
-    if (ctrl[CT_FOUND]) {
-        ctrl[CT_LEVEL] += 1;
-        ctrl[CT_FOUND] = 0;
-    } else {
-        ctrl[CT_DONE] = 1;
-    }
+    if (bfs_row(v, l, row_ptr[v] + threadIdx.x, row_ptr[v + 1], BC_BLOCK, col, level, parent)) st(ctrl + GRX_CT_FOUND, 1);
 }
 
 // A symmetric CSR leaves no vertex without a level.  One that is not symmetric can (components follow the arcs both
@@ -571,31 +554,6 @@ __global__ __launch_bounds__(BC_BLOCK) void bc_count_kernel(int64_t n, const int
     if (threadIdx.x == 0 && total) atomicAdd(ctrl + CT_NCOMP, total);
 }
 
-struct PinnedCtrl {
-    int32_t *h = nullptr;
-    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
-};
-thread_local PinnedCtrl g_ctrl;
-
-int read_ctrl(const int32_t *d_ctrl, int32_t out[CT_COUNT], hipStream_t st)
-{
-    if (!g_ctrl.h) {
-        void *h = nullptr;
-        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
-        g_ctrl.h = reinterpret_cast<int32_t *>(h);
-    }
-    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, CT_COUNT * sizeof(int32_t), st);
-    if (rc == GRX_OK) rc = grx_fetch_wait(st);
-    if (rc != GRX_OK) return rc;
-    for (int k = 0; k < CT_COUNT; ++k) out[k] = g_ctrl.h[k];
-    return GRX_OK;
-}
-
-unsigned elem_grid(int64_t n)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(n, BC_BLOCK), BC_MAX_BLOCKS));
-}
-
 int scan_exclusive(int64_t m, int32_t *a, int32_t *bsum, hipStream_t st)
 {
     const int64_t tiles = grx_ceil_div(m, BC_SCAN_TILE);
@@ -625,7 +583,7 @@ int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
     hipStream_t st = grx_stream(stream);
     const BcWs ws = carve(d_workspace, n);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
-    const unsigned egrid = elem_grid(n), hubs = (unsigned)n_hub_rows;
+    const unsigned egrid = grx_grid(n, BC_BLOCK, BC_MAX_BLOCKS), hubs = (unsigned)n_hub_rows;
     const unsigned lgrid = std::min<unsigned>(egrid, BC_LEVEL_BLOCKS);
 
     // 1. connected components
@@ -636,32 +594,27 @@ int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
     // 2. BFS from every root
     bc_bfs_init_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, ws.uf, ws.level, ws.parent, ws.size, ws.ctrl);
     GRX_LAUNCH_CHECK();
-    int32_t h[CT_COUNT] = {0, 0, 0, 0};
-    int64_t issued = 0;
-    while (!h[CT_DONE]) {
-        // a BFS has at most n - 1 levels; one more launch finds the empty frontier
-        GRX_REQUIRE(issued <= n + 1, "grx_biconnected: the BFS did not end after %lld levels", (long long)issued);
-        for (int k = 0; k < BC_LEVEL_BATCH; ++k, ++issued) {
+    int32_t h[CT_COUNT];
+    // a BFS has at most n - 1 levels; one more launch finds the empty frontier
+    int rc = grx_run_rounds(
+        "grx_biconnected: the BFS did not end after %lld levels", BC_LEVEL_BATCH, n + 1, CT_COUNT, ws.ctrl, h, st, [&] {
             if (hubs)
                 bc_bfs_hub_kernel<<<hubs, BC_BLOCK, 0, st>>>(d_row_ptr, d_col, d_hub_rows, ws.level, ws.parent,
                                                              ws.ctrl);
             bc_bfs_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, d_row_ptr, d_col, hub_degree, ws.level, ws.parent, ws.ctrl);
-            bc_bfs_finalize_kernel<<<1, 1, 0, st>>>(ws.ctrl);
-            GRX_LAUNCH_CHECK();
-        }
-        const int rc = read_ctrl(ws.ctrl, h, st);
-        if (rc != GRX_OK) return rc;
-    }
-    const int D = h[CT_LEVEL];                               // levels 0 .. D
+            return grx_frontier_advance(ws.ctrl, st);
+        });
+    if (rc != GRX_OK) return rc;
+    const int D = h[GRX_CT_LEVEL];                           // levels 0 .. D (the level word stays the deepest level)
     GRX_REQUIRE(D >= 0 && D < n, "grx_biconnected: BFS depth %d", D);
     //    buckets: offs[l] .. offs[l + 1]
     const int64_t chunk = grx_ceil_div(n, egrid);
     bc_bfs_close_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, ws.level, ws.parent);
-    bc_fill_kernel<<<elem_grid(D + 2), BC_BLOCK, 0, st>>>(D + 2, ws.offs, 0);
-    bc_fill_kernel<<<elem_grid(D + 2), BC_BLOCK, 0, st>>>(D + 2, ws.top, 0);
+    grx_fill32(ws.offs, D + 2, 0, st);
+    grx_fill32(ws.top, D + 2, 0, st);
     bc_level_hist_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, chunk, ws.level, ws.offs);
     GRX_LAUNCH_CHECK();
-    int rc = scan_exclusive(D + 2, ws.offs, ws.bsum, st);
+    rc = scan_exclusive(D + 2, ws.offs, ws.bsum, st);
     if (rc != GRX_OK) return rc;
     bc_level_scatter_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, chunk, ws.level, ws.offs, ws.top, ws.order);
     // 3. subtree sizes
@@ -700,7 +653,7 @@ int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
     bc_count_kernel<<<egrid, BC_BLOCK, 0, st>>>(n, ws.top, d_count, ws.ctrl);
     GRX_LAUNCH_CHECK();
     if (n_components) {
-        rc = read_ctrl(ws.ctrl, h, st);
+        rc = grx_read_ctrl(ws.ctrl, CT_COUNT, h, st);
         if (rc != GRX_OK) return rc;
         *n_components = h[CT_NCOMP];
     }

@@ -17,9 +17,8 @@
 //   reach(v) += c,  dsum(v) += d c  (int64, exact: dsum <= n^2 < 2^62),
 //   harm(v)  += c q(d), q(d) = fl(1 / d) 2^84 as an unsigned 128-bit integer: for d < 2^31 the fp64 value fl(1 / d)
 //              is a whole multiple of 2^-84, and the sum stays below n_sources 2^84 < 2^115.
-// A one-thread finalize advances the device level or sets `done` when a level reached nothing new; every launch
-// returns at once after `done`, so the host enqueues levels in batches and reads (done, level) back once per
-// batch.  At the end harmonic(v) = harm(v) 2^-84, rounded once to nearest-even: the correctly rounded sum of the fp64
+// The levels run as a device-steered round loop (grx_common.h).
+// At the end harmonic(v) = harm(v) 2^-84, rounded once to nearest-even: the correctly rounded sum of the fp64
 // terms fl(1 / d), the same bits for every W, source order and run.  Integer arithmetic only; no floating-point
 // atomics (the source bits are set with integer atomicOr).
 #pragma clang fp contract(off)
@@ -34,10 +33,9 @@ constexpr int CL_BLOCK = 256;
 constexpr int CL_MAX_WORDS = 16;
 constexpr int CL_LEVEL_BATCH = 8;                            // levels enqueued between two read-backs
 constexpr int CL_MAX_ROW_BLOCKS = 8192;
+constexpr int CL_MAX_BLOCKS = 2048;                           // grid of the per-element launch
 constexpr size_t CL_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of W
 constexpr int CL_HARM_SHIFT = 84;                            // harm(v) holds sum c fl(1 / d) scaled by 2^84
-
-enum { CT_DONE = 0, CT_LEVEL, CT_FOUND, CT_COUNT };
 
 bool valid_words(int w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; }
 
@@ -134,12 +132,6 @@ __device__ __forceinline__ void add_level(int64_t v, int c, int d, int64_t *__re
     harm[2 * v + 1] = (uint64_t)(h >> 64);
 }
 
-__global__ __launch_bounds__(CL_BLOCK) void cl_zero_kernel(int64_t words, uint64_t *__restrict__ a)
-{
-    for (int64_t i = (int64_t)blockIdx.x * CL_BLOCK + threadIdx.x; i < words; i += (int64_t)gridDim.x * CL_BLOCK)
-        a[i] = 0;
-}
-
 // lane b < count: bit b of source s_b's visited and frontier words (integer atomics: one node may be the source of
 // several lanes of a word); level 0
 __global__ __launch_bounds__(CL_BLOCK) void cl_source_init_kernel(int64_t n, int W, int count,
@@ -156,7 +148,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_source_init_kernel(int64_t n, int
         atomicOr(reinterpret_cast<unsigned long long *>(&visited[cell]), bit);
         atomicOr(reinterpret_cast<unsigned long long *>(&f0[cell]), bit);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl[CT_DONE] = 0; ctrl[CT_LEVEL] = 0; ctrl[CT_FOUND] = 0; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl[GRX_CT_DONE] = 0; ctrl[GRX_CT_LEVEL] = 0; ctrl[GRX_CT_FOUND] = 0; }
 }
 
 // one level, rows up to hub_degree arcs: W lanes per node, CL_BLOCK / W nodes per workgroup and grid step
@@ -169,8 +161,8 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_level_kernel(int64_t n, const int
                                                             uint64_t *__restrict__ harm, int32_t *__restrict__ ctrl)
 {
     constexpr int GROUPS = CL_BLOCK / W;
-    if (ctrl[CT_DONE]) return;
-    const int l = ctrl[CT_LEVEL];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL];
     const uint64_t *F = (l & 1) ? f1 : f0;
     uint64_t *Fn = (l & 1) ? f0 : f1;
     const int w = threadIdx.x % W;
@@ -199,7 +191,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_level_kernel(int64_t n, const int
             found = 1;
         }
     }
-    if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[CT_FOUND] = 1;
+    if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[GRX_CT_FOUND] = 1;
 }
 
 // one level, hub rows: one workgroup per hub row; CL_BLOCK / W lane groups take every (CL_BLOCK / W)-th arc
@@ -216,8 +208,8 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_level_hub_kernel(const int64_t *_
 {
     constexpr int GROUPS = CL_BLOCK / W;
     __shared__ uint64_t part[CL_BLOCK];
-    if (ctrl[CT_DONE]) return;
-    const int l = ctrl[CT_LEVEL];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL];
     const uint64_t *F = (l & 1) ? f1 : f0;
     uint64_t *Fn = (l & 1) ? f0 : f1;
     const int t = threadIdx.x, w = t % W;
@@ -240,19 +232,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_level_hub_kernel(const int64_t *_
     }
     if (t == 0 && c) {
         add_level(v, c, l + 1, reach, dsum, harm);
-        ctrl[CT_FOUND] = 1;
-    }
-}
-
-// one thread: next level, or done when this level reached nothing new
-__global__ void cl_finalize_kernel(int32_t *__restrict__ ctrl)
-{
-    if (ctrl[CT_DONE]) return;
-    if (ctrl[CT_FOUND]) {
-        ctrl[CT_LEVEL] += 1;
-        ctrl[CT_FOUND] = 0;
-    } else {
-        ctrl[CT_DONE] = 1;
+        ctrl[GRX_CT_FOUND] = 1;
     }
 }
 
@@ -280,32 +260,6 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_harmonic_kernel(int64_t n, const 
     }
 }
 
-struct PinnedCtrl {
-    int32_t *h = nullptr;
-    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
-};
-thread_local PinnedCtrl g_ctrl;
-
-int read_ctrl(const int32_t *d_ctrl, int32_t out[2], hipStream_t st)
-{
-    if (!g_ctrl.h) {
-        void *h = nullptr;
-        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
-        g_ctrl.h = reinterpret_cast<int32_t *>(h);
-    }
-    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, 8, st);
-    if (rc == GRX_OK) rc = grx_fetch_wait(st);
-    if (rc != GRX_OK) return rc;
-    out[0] = g_ctrl.h[CT_DONE];
-    out[1] = g_ctrl.h[CT_LEVEL];
-    return GRX_OK;
-}
-
-int elem_grid(int64_t n)
-{
-    return (int)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(n, CL_BLOCK), 2048));
-}
-
 struct Args {
     int64_t n;
     const int64_t *row_ptr;
@@ -322,23 +276,19 @@ template <int W>
 int run(const Args &a, const ClWs &ws, hipStream_t st)
 {
     const int64_t n = a.n;
-    const unsigned row_blocks = (unsigned)std::max<int64_t>(
-        1, std::min<int64_t>(grx_ceil_div(n, CL_BLOCK / W), CL_MAX_ROW_BLOCKS));
+    const unsigned row_blocks = grx_grid(n, CL_BLOCK / W, CL_MAX_ROW_BLOCKS);
     const int64_t cells = n * W;
     for (int64_t first = 0; first < a.n_sources; first += 64 * W) {
         const int count = (int)std::min<int64_t>(64 * W, a.n_sources - first);
-        cl_zero_kernel<<<elem_grid(cells), CL_BLOCK, 0, st>>>(cells, ws.visited);
-        cl_zero_kernel<<<elem_grid(cells), CL_BLOCK, 0, st>>>(cells, ws.f0);
+        grx_fill64(ws.visited, cells, 0, st);
+        grx_fill64(ws.f0, cells, 0, st);
         cl_source_init_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
             n, W, count, a.sources + first, ws.visited, ws.f0, ws.ctrl);
         GRX_LAUNCH_CHECK();
-        int32_t h[2] = {0, 0};
-        int64_t issued = 0;
-        while (!h[0]) {
-            // a BFS has at most n - 1 levels; one more launch finds the empty frontier
-            GRX_REQUIRE(issued <= n + 1, "grx_distance_sums: the BFS did not end after %lld levels",
-                        (long long)issued);
-            for (int k = 0; k < CL_LEVEL_BATCH; ++k, ++issued) {
+        int32_t h[2];
+        // a BFS has at most n - 1 levels; one more launch finds the empty frontier
+        const int rc = grx_run_rounds(
+            "grx_distance_sums: the BFS did not end after %lld levels", CL_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
                 if (a.n_hub_rows)
                     cl_level_hub_kernel<W><<<(unsigned)a.n_hub_rows, CL_BLOCK, 0, st>>>(
                         a.row_ptr, a.col, a.hub_rows, count, ws.visited, ws.f0, ws.f1, a.reach, a.dsum, ws.harm,
@@ -346,14 +296,11 @@ int run(const Args &a, const ClWs &ws, hipStream_t st)
                 cl_level_kernel<W><<<row_blocks, CL_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.hub_degree, count,
                                                                     ws.visited, ws.f0, ws.f1, a.reach, a.dsum,
                                                                     ws.harm, ws.ctrl);
-                cl_finalize_kernel<<<1, 1, 0, st>>>(ws.ctrl);
-                GRX_LAUNCH_CHECK();
-            }
-            const int rc = read_ctrl(ws.ctrl, h, st);
-            if (rc != GRX_OK) return rc;
-        }
+                return grx_frontier_advance(ws.ctrl, st);
+            });
+        if (rc != GRX_OK) return rc;
     }
-    cl_harmonic_kernel<<<elem_grid(n), CL_BLOCK, 0, st>>>(n, ws.harm, a.harmonic);
+    cl_harmonic_kernel<<<grx_grid(n, CL_BLOCK, CL_MAX_BLOCKS), CL_BLOCK, 0, st>>>(n, ws.harm, a.harmonic);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }
@@ -388,10 +335,9 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
     const ClWs ws = carve(d_workspace, n, W);
     const Args a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
                  d_sources, n_sources, d_reach, d_dsum, d_harmonic};
-    const int egrid = elem_grid(n);
-    cl_zero_kernel<<<egrid, CL_BLOCK, 0, st>>>(n, reinterpret_cast<uint64_t *>(d_reach));
-    cl_zero_kernel<<<egrid, CL_BLOCK, 0, st>>>(n, reinterpret_cast<uint64_t *>(d_dsum));
-    cl_zero_kernel<<<elem_grid(2 * n), CL_BLOCK, 0, st>>>(2 * n, ws.harm);
+    grx_fill64(reinterpret_cast<uint64_t *>(d_reach), n, 0, st);
+    grx_fill64(reinterpret_cast<uint64_t *>(d_dsum), n, 0, st);
+    grx_fill64(ws.harm, 2 * n, 0, st);
     GRX_LAUNCH_CHECK();
     switch (W) {
     case 1: return run<1>(a, ws, st);

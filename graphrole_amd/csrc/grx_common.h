@@ -71,6 +71,59 @@ int grx_fetch_begin(void *h_dst_pinned, const void *d_src, size_t bytes, hipStre
 int grx_fetch_wait(hipStream_t st);
 static inline size_t grx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Workgroups of a grid-stride launch: one per `per_block` items, at least 1 and at most `cap`.
+static inline unsigned grx_grid(int64_t items, int64_t per_block, int64_t cap)
+{
+    const int64_t g = grx_ceil_div(items, per_block);
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+// Grid-stride stores of one constant into `count` 32-bit / 64-bit words (zeroing doubles and int64 is grx_fill64 with
+// 0): 256 threads, grx_grid(count, 256, 2048) workgroups.  Launch only: the caller's GRX_LAUNCH_CHECK covers them.
+void grx_fill32(int32_t *d_dst, int64_t count, int32_t value, hipStream_t st);
+void grx_fill64(uint64_t *d_dst, int64_t count, uint64_t value, hipStream_t st);
+
+// ---- round loops the device steers (BFS levels, peeling rounds, power iterations) -------------------------------
+// A loop whose trip count only the device knows keeps a few int32 control words at the end of its workspace.  In every
+// layout word 0 is `done` and word 1 the counter (BFS level, peeling layer, iteration count); the BFS loops share the
+// three words below, and a file with more words continues its own enum after them (grx_kcore.hip's KT_* and
+// grx_measures.hip's CT_ITERS name words 0 and 1 their own way).  Every kernel of a round returns at once when `done`
+// is set, and a one-thread kernel at the end of the round advances the counter or sets `done`.  So the host enqueues
+// a fixed batch of rounds without waiting, reads the control words back once per batch (grx_read_ctrl: grx_fetch_begin
+// + grx_fetch_wait into one pinned block per host thread, allocated on first use and freed when the thread ends) and
+// repeats until `done`: the results are those of a loop that checked after every round.
+enum { GRX_CT_DONE = 0, GRX_CT_LEVEL, GRX_CT_FOUND, GRX_CT_BFS_WORDS };
+constexpr int GRX_CTRL_MAX_WORDS = 16;   // the pinned block; the widest user has 8 (grx_kcore.hip)
+
+// out[0 .. words) = d_ctrl[0 .. words) once everything queued on st has finished
+int grx_read_ctrl(const int32_t *d_ctrl, int words, int32_t *out, hipStream_t st);
+
+// the one-thread end of a BFS level: `found` set -> level += 1, found = 0; else done = 1 (the level word then holds
+// the deepest level reached); nothing once `done` is set
+int grx_frontier_advance(int32_t *d_ctrl, hipStream_t st);
+
+// Enqueues `batch` rounds (enqueue_one() launches one round, its advancing kernel last, and returns a GRX_* code),
+// reads `words` control words into h and repeats until h[0] (`done`).  Refuses with the caller's message `what` -- a
+// format with one %lld, the number of rounds issued -- once more than max_rounds have been issued.
+template <class Enqueue>
+int grx_run_rounds(const char *what, int batch, int64_t max_rounds, int words, const int32_t *d_ctrl, int32_t *h,
+                   hipStream_t st, Enqueue enqueue_one)
+{
+    for (int k = 0; k < words; ++k) h[k] = 0;
+    int64_t issued = 0;
+    while (!h[0]) {
+        GRX_REQUIRE(issued <= max_rounds, what, (long long)issued);
+        for (int k = 0; k < batch; ++k, ++issued) {
+            const int rc = enqueue_one();
+            if (rc != GRX_OK) return rc;
+            GRX_LAUNCH_CHECK();
+        }
+        const int rc = grx_read_ctrl(d_ctrl, words, h, st);
+        if (rc != GRX_OK) return rc;
+    }
+    return GRX_OK;
+}
+
 // Fixed-shape butterfly: every lane ends with the same total, the addition tree depends only
 // on WIDTH, so results are bitwise reproducible.
 template <int WIDTH>

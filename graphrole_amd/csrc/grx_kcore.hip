@@ -40,12 +40,11 @@
 // its crossing decrement (or after it left) changes nothing that is read again.  Appends go through an LDS buffer per
 // workgroup: one global atomic per workgroup and round on the list counter.
 // A one-thread finalize subtracts |F| from the alive count, advances `layer` or sets `done`, and raises the sweep flag
-// when the next list is empty; every launch returns at once after `done`, so the host enqueues KC_ROUND_BATCH rounds
-// between read-backs of (done, layer).  Integer arithmetic only; core and onion are the same in every run (the order
-// of the lists is not, and is never visible).  The CSRs must hold no self-loop (the caller's precondition).
+// when the next list is empty; the rounds run as a device-steered round loop (grx_common.h).  Integer arithmetic only;
+// core and onion are the same in every run (the order of the lists is not, and is never visible).  The CSRs must hold
+// no self-loop (the caller's precondition).
 #include "grx_common.h"
 
-#include <algorithm>
 #include <climits>
 
 namespace {
@@ -290,32 +289,6 @@ __global__ void kc_finalize_kernel(KcState s)
     ctrl[KT_LAYER] += 1;
 }
 
-struct PinnedCtrl {
-    int32_t *h = nullptr;
-    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
-};
-thread_local PinnedCtrl g_ctrl;
-
-int read_ctrl(const int32_t *d_ctrl, int32_t out[2], hipStream_t st)
-{
-    if (!g_ctrl.h) {
-        void *h = nullptr;
-        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
-        g_ctrl.h = reinterpret_cast<int32_t *>(h);
-    }
-    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, 8, st);
-    if (rc == GRX_OK) rc = grx_fetch_wait(st);
-    if (rc != GRX_OK) return rc;
-    out[0] = g_ctrl.h[KT_DONE];
-    out[1] = g_ctrl.h[KT_LAYER];
-    return GRX_OK;
-}
-
-unsigned grid_for(int64_t items, int per_block)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(items, per_block), KC_MAX_BLOCKS));
-}
-
 }  // namespace
 
 extern "C" {
@@ -347,7 +320,8 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
     const KcState s = carve(d_workspace, n, d_core, d_onion);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
     const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
-    const unsigned sweep_grid = grid_for(n, KC_BLOCK), peel_grid = grid_for(n, KC_BLOCK / KC_GROUP);
+    const unsigned sweep_grid = grx_grid(n, KC_BLOCK, KC_MAX_BLOCKS);
+    const unsigned peel_grid = grx_grid(n, KC_BLOCK / KC_GROUP, KC_MAX_BLOCKS);
 
     kc_init_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, d_row_ptr, d_in_row_ptr, s);
     if (n_hub_rows)
@@ -357,13 +331,10 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
         kc_hub_flag_kernel<<<(unsigned)grx_ceil_div(n_in_hub_rows, KC_BLOCK), KC_BLOCK, 0, st>>>(
             n, d_in_hub_rows, n_in_hub_rows, KC_IN_HUB, s.state);
     GRX_LAUNCH_CHECK();
-    int32_t h[2] = {0, 0};
-    int64_t issued = 0;
-    while (!h[0]) {
-        // every round but the last removes a node: at most n rounds
-        GRX_REQUIRE(issued <= n + 1, "grx_core_numbers: the peeling did not end after %lld rounds",
-                    (long long)issued);
-        for (int k = 0; k < KC_ROUND_BATCH; ++k, ++issued) {
+    int32_t h[2];
+    // every round but the last removes a node: at most n rounds
+    const int rc = grx_run_rounds(
+        "grx_core_numbers: the peeling did not end after %lld rounds", KC_ROUND_BATCH, n + 1, 2, s.ctrl, h, st, [&] {
             kc_min_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, s);
             kc_collect_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, s);
             if (n_hub_rows)
@@ -375,12 +346,10 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
             kc_peel_kernel<<<peel_grid, KC_BLOCK, 0, st>>>(d_row_ptr, d_col, hub_degree, d_in_row_ptr, d_in_col,
                                                            in_hub_degree, s);
             kc_finalize_kernel<<<1, 1, 0, st>>>(s);
-            GRX_LAUNCH_CHECK();
-        }
-        const int rc = read_ctrl(s.ctrl, h, st);
-        if (rc != GRX_OK) return rc;
-    }
-    if (n_rounds) *n_rounds = h[1];
+            return (int)GRX_OK;
+        });
+    if (rc != GRX_OK) return rc;
+    if (n_rounds) *n_rounds = h[KT_LAYER];
     return GRX_OK;
 }
 

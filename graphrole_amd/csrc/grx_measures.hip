@@ -4,9 +4,9 @@
 // Power iteration.  One iteration = a pull SpMV over the in-adjacency (a lane group of L lanes per row, rows longer
 // than GRX_HUB_FACTOR * L a workgroup each in a launch before it) with a fused epilogue that writes the new vector and
 // per-workgroup partials, then a one-workgroup finalize that reduces the partials in a fixed order and sets the
-// device `done` word.  Every launch of an iteration returns at once when `done` is set, so the host enqueues the
-// iterations in batches and reads (done, iterations) back once per batch: the iteration count is the one of a loop
-// that checked on the host after every iteration.  No floating-point atomics: results are the same bits run to run.
+// device `done` word.  The control words and their read-back are those of the device-steered round loops
+// (grx_common.h); the loop itself is power_run's own, bounded by max_iter and ending in GRX_ERR_NOT_CONVERGED.
+// No floating-point atomics: results are the same bits run to run.
 //
 // Compiled with -ffp-contract=off (Makefile): the local measures restate networkx's IEEE operations one by one.
 #include "grx_common.h"
@@ -256,39 +256,7 @@ __global__ __launch_bounds__(MS_BLOCK) void power_finalize_kernel(int mode, int 
     if (ta < thresh) ctrl[CT_DONE] = 1;
 }
 
-struct PinnedCtrl {
-    int32_t *h = nullptr;
-    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
-};
-thread_local PinnedCtrl g_ctrl;
-
-int read_ctrl(const int32_t *d_ctrl, int32_t out[2], hipStream_t st)
-{
-    if (!g_ctrl.h) {
-        void *h = nullptr;
-        GRX_CHECK_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped));
-        g_ctrl.h = reinterpret_cast<int32_t *>(h);
-    }
-    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, 8, st);
-    if (rc == GRX_OK) rc = grx_fetch_wait(st);
-    if (rc != GRX_OK) return rc;
-    out[0] = g_ctrl.h[0];
-    out[1] = g_ctrl.h[1];
-    return GRX_OK;
-}
-
 constexpr int MS_BATCH = 8;              // iterations enqueued between two read-backs
-
-int row_grid(int64_t n, int lanes)
-{
-    const int64_t groups = grx_ceil_div(n, MS_BLOCK / lanes);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(groups, MS_MAX_WG));
-}
-
-int elem_grid(int64_t n)
-{
-    return (int)std::max<int64_t>(1, std::min<int64_t>(grx_ceil_div(n, MS_BLOCK), MS_MAX_WG));
-}
 
 template <int L>
 void launch_pr_iter(int grid, hipStream_t st, int64_t n, const int64_t *rp, const int32_t *col, const double *w,
@@ -327,7 +295,8 @@ int power_run(bool pagerank, int64_t n, const int64_t *d_row_ptr, const int32_t 
     hipStream_t st = grx_stream(stream);
     const PowerWs ws = carve(d_ws, n);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
-    const int rgrid = row_grid(n, lanes_per_row), egrid = elem_grid(n);
+    const int rgrid = (int)grx_grid(n, MS_BLOCK / lanes_per_row, MS_MAX_WG);
+    const int egrid = (int)grx_grid(n, MS_BLOCK, MS_MAX_WG);
     const double N = (double)n;
     const double p = 1.0 / N;                               // numpy: np.repeat(1.0 / N, N)
     const double teleport = (1.0 - alpha) * p;
@@ -372,7 +341,7 @@ int power_run(bool pagerank, int64_t n, const int64_t *d_row_ptr, const int32_t 
             }
             GRX_LAUNCH_CHECK();
         }
-        const int rc = read_ctrl(ws.ctrl, h, st);
+        const int rc = grx_read_ctrl(ws.ctrl, CT_COUNT, h, st);
         if (rc != GRX_OK) return rc;
         if (h[0]) break;
     }

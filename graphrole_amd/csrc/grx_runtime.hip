@@ -169,6 +169,70 @@ int grx_fetch_wait(hipStream_t st)
     }
 }
 
+// ---- control words of the device-steered round loops, constant fills (grx_common.h) ----------------------------
+namespace {
+
+constexpr int FILL_BLOCK = 256;
+constexpr int FILL_MAX_BLOCKS = 2048;
+
+template <class T>
+__global__ __launch_bounds__(FILL_BLOCK) void grx_fill_kernel(int64_t count, T *__restrict__ a, T value)
+{
+    for (int64_t i = (int64_t)blockIdx.x * FILL_BLOCK + threadIdx.x; i < count; i += (int64_t)gridDim.x * FILL_BLOCK)
+        a[i] = value;
+}
+
+__global__ void grx_frontier_advance_kernel(int32_t *__restrict__ ctrl)
+{
+    if (ctrl[GRX_CT_DONE]) return;
+    if (ctrl[GRX_CT_FOUND]) {
+        ctrl[GRX_CT_LEVEL] += 1;
+        ctrl[GRX_CT_FOUND] = 0;
+    } else {
+        ctrl[GRX_CT_DONE] = 1;
+    }
+}
+
+struct PinnedCtrl {
+    int32_t *h = nullptr;
+    ~PinnedCtrl() { if (h) (void)hipHostFree(h); }
+};
+thread_local PinnedCtrl g_ctrl;
+
+}  // namespace
+
+void grx_fill32(int32_t *d_dst, int64_t count, int32_t value, hipStream_t st)
+{
+    grx_fill_kernel<<<grx_grid(count, FILL_BLOCK, FILL_MAX_BLOCKS), FILL_BLOCK, 0, st>>>(count, d_dst, value);
+}
+
+void grx_fill64(uint64_t *d_dst, int64_t count, uint64_t value, hipStream_t st)
+{
+    grx_fill_kernel<<<grx_grid(count, FILL_BLOCK, FILL_MAX_BLOCKS), FILL_BLOCK, 0, st>>>(count, d_dst, value);
+}
+
+int grx_frontier_advance(int32_t *d_ctrl, hipStream_t st)
+{
+    grx_frontier_advance_kernel<<<1, 1, 0, st>>>(d_ctrl);
+    GRX_LAUNCH_CHECK();
+    return GRX_OK;
+}
+
+int grx_read_ctrl(const int32_t *d_ctrl, int words, int32_t *out, hipStream_t st)
+{
+    GRX_REQUIRE(words >= 1 && words <= GRX_CTRL_MAX_WORDS, "grx_read_ctrl: %d control words", words);
+    if (!g_ctrl.h) {
+        void *h = nullptr;
+        GRX_CHECK_HIP(hipHostMalloc(&h, GRX_CTRL_MAX_WORDS * sizeof(int32_t), hipHostMallocMapped));
+        g_ctrl.h = reinterpret_cast<int32_t *>(h);
+    }
+    int rc = grx_fetch_begin(g_ctrl.h, d_ctrl, (size_t)words * sizeof(int32_t), st);
+    if (rc == GRX_OK) rc = grx_fetch_wait(st);
+    if (rc != GRX_OK) return rc;
+    for (int k = 0; k < words; ++k) out[k] = g_ctrl.h[k];
+    return GRX_OK;
+}
+
 extern "C" {
 
 int grx_trace_marker(int tag, void *stream)

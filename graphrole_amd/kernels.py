@@ -1147,12 +1147,23 @@ def row_counts(csr: DeviceCSR, add_self_loop: bool) -> torch.Tensor:
     return out
 
 
+def _csr_args(csr: Optional[DeviceCSR]) -> tuple:
+    """(row_ptr, col, hub_rows, n_hubs, lanes_per_row) of a CSR as C arguments; five nulls for None."""
+    if csr is None:
+        return (None, None, None, 0, 0)
+    return (_ptr(csr.row_ptr), _ptr(csr.col), _ptr(csr.hub_rows), csr.n_hubs, csr.lanes_per_row)
+
+
+def _workspace(symbol: str, *args) -> Tuple[torch.Tensor, int]:
+    """(uint8 device tensor, its size) of the bytes `symbol` -- a grx_*_workspace_bytes entry -- asks for."""
+    nbytes = getattr(_lib.load(), symbol)(*args)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device()), nbytes
+
+
 def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alpha: float, tol: float,
            max_iter: int, lanes: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     n = csr_in.n
-    lib = _lib.load()
-    ws_bytes = getattr(lib, name + '_workspace_bytes')(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    ws, ws_bytes = _workspace(name + '_workspace_bytes', n)
     x = torch.empty(max(n, 1), dtype=torch.float64, device=device())
     iters = ctypes.c_int(0)
     graph = (n, _ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.w))
@@ -1168,7 +1179,7 @@ def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alp
         args = graph + (_ptr(out_weight),) + hubs + (float(alpha), float(tol))
     else:
         args = graph + hubs + (float(tol),)
-    rc = getattr(lib, name)(*args, int(max_iter), _ptr(x), ctypes.byref(iters), _ptr(ws), ws_bytes, _stream())
+    rc = getattr(_lib.load(), name)(*args, int(max_iter), _ptr(x), ctypes.byref(iters), _ptr(ws), ws_bytes, _stream())
     if rc == -6:
         raise _lib.ConvergenceError(f'power iteration failed to converge within {max_iter} iterations',
                                     iterations=iters.value)
@@ -1237,17 +1248,10 @@ def betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.nda
     batch = sources per batch (a multiple of 64; 0 = the library's choice)."""
     n = csr_out.n
     src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
-    lib = _lib.load()
-    ws_bytes = lib.grx_betweenness_workspace_bytes(n, int(batch), len(src))   # sized for the B the call uses
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    ws, ws_bytes = _workspace('grx_betweenness_workspace_bytes', n, int(batch), len(src))   # for the B the call uses
     bc = torch.empty(max(n, 1), dtype=torch.float64, device=device())
-    if csr_in is None:
-        in_args = (None, None, None, 0, 0)
-    else:
-        in_args = (_ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.hub_rows), csr_in.n_hubs, csr_in.lanes_per_row)
-    _lib.call('grx_betweenness', n, _ptr(csr_out.row_ptr), _ptr(csr_out.col), _ptr(csr_out.hub_rows), csr_out.n_hubs,
-              csr_out.lanes_per_row, *in_args, _ptr(src), len(src), int(bool(endpoints)), float(scale), int(batch),
-              _ptr(bc), _ptr(ws), ws_bytes, _stream())
+    _lib.call('grx_betweenness', n, *_csr_args(csr_out), *_csr_args(csr_in), _ptr(src), len(src), int(bool(endpoints)),
+              float(scale), int(batch), _ptr(bc), _ptr(ws), ws_bytes, _stream())
     return bc
 
 
@@ -1258,14 +1262,11 @@ def distance_sums(csr_pull: DeviceCSR, sources: np.ndarray,
     reversed arcs.  words = 64-bit source words per batch (1, 2, 4, 8 or 16; 0 = the library's choice)."""
     n = csr_pull.n
     src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
-    lib = _lib.load()
-    ws_bytes = lib.grx_distance_sums_workspace_bytes(n, int(words), len(src))   # sized for the W the call uses
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    ws, ws_bytes = _workspace('grx_distance_sums_workspace_bytes', n, int(words), len(src))   # for the W the call uses
     reach = torch.empty(max(n, 1), dtype=torch.int64, device=device())
     dsum = torch.empty(max(n, 1), dtype=torch.int64, device=device())
     harmonic = torch.empty(max(n, 1), dtype=torch.float64, device=device())
-    _lib.call('grx_distance_sums', n, _ptr(csr_pull.row_ptr), _ptr(csr_pull.col), _ptr(csr_pull.hub_rows),
-              csr_pull.n_hubs, csr_pull.lanes_per_row, _ptr(src), len(src), int(words), _ptr(reach), _ptr(dsum),
+    _lib.call('grx_distance_sums', n, *_csr_args(csr_pull), _ptr(src), len(src), int(words), _ptr(reach), _ptr(dsum),
               _ptr(harmonic), _ptr(ws), ws_bytes, _stream())
     return reach, dsum, harmonic
 
@@ -1277,16 +1278,13 @@ def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor,
     component of the tree edge (parent[c], c) (-1 for a root), n_components).  want_forest=False passes NULL for
     parent and label (both None then)."""
     n = csr.n
-    lib = _lib.load()
-    ws_bytes = lib.grx_biconnected_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    ws, ws_bytes = _workspace('grx_biconnected_workspace_bytes', n)
     count = torch.empty(max(n, 1), dtype=torch.int64, device=device())
     parent = torch.empty(max(n, 1), dtype=torch.int32, device=device()) if want_forest else None
     label = torch.empty(max(n, 1), dtype=torch.int32, device=device()) if want_forest else None
     n_components = ctypes.c_int64(0)
-    _lib.call('grx_biconnected', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(csr.hub_rows), csr.n_hubs,
-              csr.lanes_per_row, _ptr(count), _ptr(parent), _ptr(label), ctypes.byref(n_components), _ptr(ws), ws_bytes,
-              _stream())
+    _lib.call('grx_biconnected', n, *_csr_args(csr), _ptr(count), _ptr(parent), _ptr(label),
+              ctypes.byref(n_components), _ptr(ws), ws_bytes, _stream())
     return count, parent, label, int(n_components.value)
 
 
@@ -1297,17 +1295,10 @@ def core_numbers(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR] = None,
     symmetric; otherwise the in-adjacency of a directed graph (degree = in + out).  want_onion=False passes NULL for
     onion (None then)."""
     n = csr_out.n
-    lib = _lib.load()
-    ws_bytes = lib.grx_core_numbers_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device())
+    ws, ws_bytes = _workspace('grx_core_numbers_workspace_bytes', n)
     core = torch.empty(max(n, 1), dtype=torch.int64, device=device())
     onion = torch.empty(max(n, 1), dtype=torch.int64, device=device()) if want_onion else None
-    if csr_in is None:
-        in_args = (None, None, None, 0, 0)
-    else:
-        in_args = (_ptr(csr_in.row_ptr), _ptr(csr_in.col), _ptr(csr_in.hub_rows), csr_in.n_hubs, csr_in.lanes_per_row)
     n_rounds = ctypes.c_int64(0)
-    _lib.call('grx_core_numbers', n, _ptr(csr_out.row_ptr), _ptr(csr_out.col), _ptr(csr_out.hub_rows), csr_out.n_hubs,
-              csr_out.lanes_per_row, *in_args, _ptr(core), _ptr(onion), ctypes.byref(n_rounds), _ptr(ws), ws_bytes,
-              _stream())
+    _lib.call('grx_core_numbers', n, *_csr_args(csr_out), *_csr_args(csr_in), _ptr(core), _ptr(onion),
+              ctypes.byref(n_rounds), _ptr(ws), ws_bytes, _stream())
     return core, onion, int(n_rounds.value)

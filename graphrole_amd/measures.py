@@ -186,10 +186,7 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
     def peeling():
         # one kernel call for both columns; the distinct arcs, out and (directed) in
         if 'peeling' not in cache:
-            s_out, s_in = graph._structure_csrs()
-            if directed and s_in is None:
-                raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; '
-                                          f'core_number cannot be computed on it')
+            s_out, s_in = _structure_pair(graph, 'core_number')
             cache['peeling'] = K.core_numbers(s_out, s_in if directed else None, 'onion_layer' in names)
         return cache['peeling']
 
@@ -211,10 +208,7 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col, dt = local()[1], np.dtype('float64')
         elif nm == 'betweenness_centrality':
             # BFS walks G[v]: the distinct arcs, out and (directed) in, not a neighbour multiset
-            s_out, s_in = graph._structure_csrs()
-            if directed and s_in is None:
-                raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; '
-                                          f'betweenness_centrality cannot be computed on it')
+            s_out, s_in = _structure_pair(graph, 'betweenness_centrality')
             col = K.betweenness(s_out, s_in if directed else None, np.asarray(host.inv)[sources], endpoints,
                                 _rescale_factor(host.n, normalized, directed, k, endpoints))
             dt = np.dtype('float64')
@@ -241,6 +235,16 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
     frame = graph._frame(names, cols, dtypes)
     frame.attrs['iterations'] = iterations
     return frame
+
+
+def _structure_pair(graph, what: str):
+    """``graph._structure_csrs()``: (out CSR, in CSR) of the distinct arcs; refuses a directed graph whose adapter has
+    no in-adjacency, naming the measure `what`."""
+    s_out, s_in = graph._structure_csrs()
+    if graph.directed and s_in is None:
+        raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; '
+                                  f'{what} cannot be computed on it')
+    return s_out, s_in
 
 
 def _py_random_state(seed) -> random.Random:
@@ -324,13 +328,9 @@ def _distance_sums(graph, K, sources: np.ndarray, reverse: bool):
     """kernels.distance_sums from `sources` (internal row ids) along the distinct arcs (``_structure_csrs``: G[v],
     parallel edges once): the out-arcs (pulled over the in-adjacency), or with `reverse` the reversed arcs (pulled over
     the out-adjacency)."""
-    s_out, s_in = graph._structure_csrs()
     if not graph.directed or reverse:
-        return K.distance_sums(s_out, sources)
-    if s_in is None:
-        raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; closeness and '
-                                  f'harmonic centrality cannot be computed on it')
-    return K.distance_sums(s_in, sources)
+        return K.distance_sums(graph._structure_csrs()[0], sources)
+    return K.distance_sums(_structure_pair(graph, 'closeness and harmonic centrality')[1], sources)
 
 
 def _closeness(reach: np.ndarray, dsum: np.ndarray, n: int, wf_improved: bool) -> np.ndarray:
