@@ -13,7 +13,7 @@
 //   * 'count' / 'size': the number of neighbours.
 // API completeness, not a tuned path: one lane per (row, column) for the integer
 // aggregations, one wavefront per row for the median.
-#include "grx_common.h"
+#include "grx_sort.h"
 
 namespace {
 
@@ -73,18 +73,6 @@ __global__ __launch_bounds__(256) void count_kernel(const int64_t *__restrict__ 
 }
 
 // ---- median -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t med_key(double x)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);        // total order of the doubles as unsigned integers
-}
-
-__device__ __forceinline__ double med_val(uint64_t k)
-{
-    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
 // vals[e] = order key of column c of neighbour col[e] for the adjacency entries of rows [row_begin, row_end)
 __global__ __launch_bounds__(256) void med_gather_kernel(const int32_t *__restrict__ col, const double *__restrict__ rows,
                                                          int64_t row_stride, int c, int64_t e_begin, int64_t e_end,
@@ -92,7 +80,7 @@ __global__ __launch_bounds__(256) void med_gather_kernel(const int32_t *__restri
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = e_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < e_end; e += stride)
-        vals[e - e_begin] = med_key(rows[(int64_t)col[e] * row_stride + c] + 0.0);
+        vals[e - e_begin] = f64_to_key(rows[(int64_t)col[e] * row_stride + c] + 0.0);
 }
 
 // one wavefront per row: the k-th smallest (0-based) of keys[0..d), and how many keys are <= it
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(256) void med_select_kernel(const int64_t *__restri
             int64_t n_le = 0;
             const int64_t k = (d - 1) / 2;                       // lower middle
             const uint64_t ka = med_select(keys, d, k, &n_le, s_hist[wave]);
-            const double a = med_val(ka);
+            const double a = key_to_f64(ka);
             if (d & 1) {
                 res = a;
             } else {
@@ -174,7 +162,7 @@ __global__ __launch_bounds__(256) void med_select_kernel(const int64_t *__restri
                         const uint64_t o = __shfl_xor(mn, off, 64);
                         mn = o < mn ? o : mn;
                     }
-                    bval = med_val(mn);
+                    bval = key_to_f64(mn);
                 }
                 res = (a + bval) / 2.0;                          // numpy: mean of the two middle elements
             }

@@ -124,6 +124,21 @@ int grx_run_rounds(const char *what, int batch, int64_t max_rounds, int words, c
     return GRX_OK;
 }
 
+// ---- entry points below the C ABI that one translation unit offers the others -----------------------------------
+// grx_sort.hip.  Workspace of the first and the last: grx_sort_workspace_bytes(n, ncols) resp. (n, 1), laid out as in
+// grx_sort_columns; of the pairs form: grx_internal_sort_pairs_workspace_bytes(n).
+int grx_internal_sort_columns(int64_t n, int ncols, const double *cols, int64_t ld, double *out, int64_t out_ld,
+                              void *workspace, hipStream_t st);
+int grx_internal_sort_pairs(int64_t n, const double *col, double *out, uint32_t *perm, void *workspace, hipStream_t st);
+size_t grx_internal_sort_pairs_workspace_bytes(int64_t n);
+int grx_internal_sort_u64(int64_t n, const uint64_t *keys, uint64_t *out, void *workspace, hipStream_t st);
+// grx_prune.hip: grx_vertical_log_bin_typed with a place for the outcome flags (d_status, two words; may be NULL)
+int grx_internal_vertical_log_bin(int64_t n, int ncols, const double *d_cols, int64_t ld, const uint8_t *h_is_i64, double frac,
+                                  uint8_t *d_bins, int64_t ld_bins, int32_t *d_nbins, void *d_workspace,
+                                  size_t workspace_bytes, int32_t *d_status, void *stream);
+// grx_graph.hip
+int64_t grx_internal_plan_max_degree(const grx_aggregate_plan *plan);
+
 // Fixed-shape butterfly: every lane ends with the same total, the addition tree depends only
 // on WIDTH, so results are bitwise reproducible.
 template <int WIDTH>

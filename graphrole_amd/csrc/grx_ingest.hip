@@ -14,9 +14,6 @@
 // All results are integers (and copied weights): bit-identical to the host construction (tests compare them).
 #include "grx_common.h"
 
-int grx_internal_sort_u64(int64_t n, const uint64_t *keys, uint64_t *out, void *workspace, hipStream_t st);
-extern "C" size_t grx_sort_workspace_bytes(int64_t n, int ncols);
-
 namespace {
 
 constexpr uint64_t ING_SENTINEL = ~0ull;

@@ -57,9 +57,6 @@
 // __dmul_rn / __dadd_rn are plain * and + and do not prevent it -- and the seeding needs the SAME distance bits
 // wherever a distance is evaluated (the consistency check of km_prep_kernel caught exactly that).
 
-int grx_internal_sort_pairs(int64_t n, const double *col, double *out, uint32_t *perm, void *workspace, hipStream_t st);
-size_t grx_internal_sort_pairs_workspace_bytes(int64_t n);
-
 namespace {
 
 typedef __int128 i128;

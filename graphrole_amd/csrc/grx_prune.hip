@@ -1,469 +1,24 @@
 // grx_prune.hip -- vertical logarithmic binning and pairwise Chebyshev distance.
 //
-// graphrole/features/prune.py:13-56 needs, per column, the sorted values (np.unique + cumsum),
-// a short walk that picks the bin thresholds, and a relabelling pass.  On the GPU:
-//   1. batched LSD radix sort of the fp64 columns (8 passes x 8 bits, keys only)
-//        tile_count_kernel -> scan_kernel -> scatter_kernel        (HBM bound, wave ballots)
-//   2. bin_threshold_kernel : one wavefront per column walks the sorted column; the end of a
-//        tie run is found with a 64-ary ballot search                (latency bound, tiny)
-//   3. bin_assign_kernel    : each value -> lower_bound over <=128 thresholds held in LDS
-//   4. chebyshev_kernel     : max_i |bin_p[i]-bin_q[i]| for column pairs, LDS-tiled rows,
-//        integer atomicMax into the F x F matrix (prune.py:108)
-// All integer work: results are bit-exact functions of the input columns.
-#include "grx_common.h"
+// graphrole/features/prune.py:13-56 sorts every column (np.unique + cumsum), walks ~20 bin thresholds down the
+// sorted values and relabels.  The walk needs those order statistics and the ends of their tie runs, not a sorted
+// column, so neither path below sorts one completely:
+//   default          sel_map -> sel_hist -> sel_walk1 -> sel_collect -> sel_sort -> sel_walk2: a monotone bucket map
+//                    from samples, one histogram pass, the walk over bucket boundaries, and an exact walk over
+//                    the few buckets a threshold can fall into (the block comment above SEL_NB)
+//   GRX_BIN_SORT=1   the window sort: key_bits -> bin_plan, four rounds of tile_count2 -> scan_rows2 -> scatter2
+//                    over the key bytes that vary, then bin_threshold2 (the block comment above BinPlanCol).  With
+//                    the library's full radix sort, grx_sort.hip, it shares grx_sort.h (tile shape, order keys,
+//                    workspace plan) and no kernel.
+//   both             bin_assign_kernel / sel_assign_kernel: each value -> lower_bound over <= 128 thresholds in LDS
+// chebyshev_kernel: max_i |bin_p[i] - bin_q[i]| for column pairs, LDS-tiled rows, integer atomicMax into the
+// F x F matrix (prune.py:108).
+// All integer work: results are bit-exact functions of the input columns, and the two paths give the same bins.
+#include "grx_sort.h"
 
 #include <cstdlib>
 
 namespace {
-
-constexpr int SORT_THREADS = 256;
-constexpr int SORT_ITEMS = 16;
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;     // 4096 keys per workgroup
-constexpr int RADIX = 256;
-
-__device__ __forceinline__ uint64_t f64_to_key(double x)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    return b ^ ((b >> 63) ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double key_to_f64(uint64_t k)
-{
-    const uint64_t b = k ^ ((k >> 63) ? 0x8000000000000000ull : 0xFFFFFFFFFFFFFFFFull);
-    return __longlong_as_double((long long)b);
-}
-
-// Pass skipping (grx_vertical_log_bin only): a byte position that is constant over a whole column
-// makes its LSD pass the identity permutation.  Pass 0's counting kernel also accumulates the OR of
-// the keys and of their complements; scan pass 0 turns them into flags[pass][col].  A skipped pass
-// launches nothing useful (every workgroup returns at once) and does not flip the ping-pong, so scan
-// pass 0 also records the buffer each column is in before every pass: 0 = the fp64 input, 1 = bufA,
-// 2 = bufB (one byte for a workgroup to read before it can issue its loads).  flags == nullptr: plain
-// sort, explicit src / dst.
-struct SkipCtl {
-    uint8_t *flags;            // [9][ncols]: PASS_SKIPPED, or the buffer the column is in before pass p (row 8: at the end)
-    uint64_t *bits;            // [ncols][ntiles][2]: per tile, OR of the keys and OR of their complements
-    const double *cols;
-    int64_t cols_ld;
-    uint64_t *buf_a, *buf_b;   // column stride n
-    int ncols;
-};
-
-constexpr uint8_t PASS_SKIPPED = 0xFF;
-
-// Load the ITEMS keys of this thread.  Wave w of the tile owns the contiguous slice
-// [w*64*ITEMS, (w+1)*64*ITEMS); item i of lane l is element i*64 + l of that slice, so
-// (wave, item, lane) order == memory order (needed for LSD stability) and loads coalesce.
-// The loads are issued back to back from clamped addresses and converted / masked afterwards, behind a scheduling
-// barrier: a load inside `if (idx < n)` -- or a conversion next to it -- makes hipcc wait for every load before it
-// issues the next one (s_waitcnt vmcnt(0) sixteen times per thread; found in the ISA).
-template <bool from_f64>
-__device__ __forceinline__ void load_keys(const void *__restrict__ src, int64_t n, int64_t tile_base,
-                                          uint64_t (&keys)[SORT_ITEMS], uint32_t &valid_mask)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t base = tile_base + (int64_t)wave * 64 * SORT_ITEMS + lane;
-    const int64_t last = n > 0 ? n - 1 : 0;
-    uint64_t raw[SORT_ITEMS];
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        const int64_t idx = base + (int64_t)i * 64;
-        raw[i] = reinterpret_cast<const uint64_t *>(src)[idx < n ? idx : last];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    valid_mask = 0;
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        const bool ok = base + (int64_t)i * 64 < n;
-        valid_mask |= ok ? 1u << i : 0u;
-        const uint64_t k = from_f64 ? f64_to_key(__longlong_as_double((long long)raw[i])) : raw[i];
-        keys[i] = ok ? k : 0xFFFFFFFFFFFFFFFFull;
-    }
-}
-
-// hist layout per column: [RADIX][ntiles] (digit-major) so one flat exclusive scan yields the
-// global output offset of (digit, tile).
-template <bool FROM_F64>
-__global__ __launch_bounds__(SORT_THREADS) void tile_count_kernel(
-    const void *__restrict__ src, int64_t src_ld, int64_t n, int shift, int ntiles,
-    uint32_t *__restrict__ hist, SkipCtl ctl)
-{
-    __shared__ uint32_t cnt[RADIX];
-    const int col = blockIdx.y, tile = blockIdx.x;
-    const int pass = shift >> 3;
-    const char *csrc = reinterpret_cast<const char *>(src) + (size_t)col * src_ld * 8;
-    bool from_f64 = FROM_F64;
-    if (ctl.flags && pass > 0) {
-        const int cur = ctl.flags[pass * ctl.ncols + col];
-        if (cur == PASS_SKIPPED) return;                        // constant byte: nothing to count
-        from_f64 = cur == 0;
-        csrc = cur == 0 ? reinterpret_cast<const char *>(ctl.cols + (size_t)col * ctl.cols_ld)
-                        : reinterpret_cast<const char *>((cur == 1 ? ctl.buf_a : ctl.buf_b) + (size_t)col * n);
-    }
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint64_t keys[SORT_ITEMS];
-    uint32_t vm;
-    // one uniform branch around the sixteen loads (fp64 input after pass 0 only when every lower byte was constant)
-    if (FROM_F64 || from_f64) load_keys<true>(csrc, n, (int64_t)tile * SORT_TILE, keys, vm);
-    else load_keys<false>(csrc, n, (int64_t)tile * SORT_TILE, keys, vm);
-    const int lane = threadIdx.x & 63;
-    if (ctl.flags && pass == 0) {
-        // which bit positions vary over the column: OR of the keys and OR of their complements
-        uint64_t o = 0, z = 0;
-#pragma unroll
-        for (int i = 0; i < SORT_ITEMS; ++i)
-            if ((vm >> i) & 1u) { o |= keys[i]; z |= ~keys[i]; }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            o |= __shfl_xor(o, off, 64);
-            z |= __shfl_xor(z, off, 64);
-        }
-        // per-tile pair, OR-ed over the tiles by scan pass 0 (no atomics: every wave of the first
-        // resident batch would hit the same address at once)
-        __shared__ uint64_t wbits[4][2];
-        if (lane == 0) { wbits[threadIdx.x >> 6][0] = o; wbits[threadIdx.x >> 6][1] = z; }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            const int k = threadIdx.x;
-            ctl.bits[((size_t)col * ntiles + tile) * 2 + k] = wbits[0][k] | wbits[1][k] | wbits[2][k] | wbits[3][k];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        // same-address LDS atomics serialise lane by lane; columns of small integers (degrees, their
-        // sums) have whole wavefronts agreeing on most digits: count those with one atomic
-        const bool valid = (vm >> i) & 1u;
-        const uint32_t d = (uint32_t)(keys[i] >> shift) & 0xFF;
-        const uint64_t active = __ballot(valid);
-        if (active == 0) continue;                              // uniform over the wave
-        const int leader = __ffsll((long long)active) - 1;
-        const uint32_t d0 = __shfl(d, leader, 64);
-        if (__ballot(valid && d != d0) == 0) {
-            if (lane == leader) atomicAdd(&cnt[d0], (uint32_t)__popcll(active));
-        } else if (valid) {
-            atomicAdd(&cnt[d], 1u);
-        }
-    }
-    __syncthreads();
-    hist[((size_t)col * RADIX + threadIdx.x) * ntiles + tile] = cnt[threadIdx.x];
-}
-
-// scan_rows_kernel: per (column, digit) exclusive scan of the digit-major counter table
-// hist[RADIX][ntiles] across tiles, digit total -> tot.  scatter_kernel scans the 256 digit totals
-// itself (digit base) and adds it to the per-tile offset.
-__global__ __launch_bounds__(64) void scan_rows_kernel(uint32_t *__restrict__ hist, int ntiles,
-                                                       uint32_t *__restrict__ tot, SkipCtl ctl, int pass)
-{
-    const int d = blockIdx.x, col = blockIdx.y, lane = threadIdx.x;
-    if (ctl.flags) {
-        if (pass > 0 && ctl.flags[pass * ctl.ncols + col] == PASS_SKIPPED) return;
-        if (pass == 0 && d == 0) {
-            // a bit varies iff it is set in some key and clear in another
-            uint64_t o = 0, z = 0;
-            for (int t = lane; t < ntiles; t += 64) {
-                o |= ctl.bits[((size_t)col * ntiles + t) * 2];
-                z |= ctl.bits[((size_t)col * ntiles + t) * 2 + 1];
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                o |= __shfl_xor(o, off, 64);
-                z |= __shfl_xor(z, off, 64);
-            }
-            const uint64_t varying = o & z;
-            if (lane == 0) {
-                int cur = 0;
-                for (int p = 0; p < 8; ++p) {
-                    const bool skip = ((varying >> (8 * p)) & 0xFF) == 0;
-                    ctl.flags[p * ctl.ncols + col] = skip ? PASS_SKIPPED : (uint8_t)cur;
-                    if (!skip) cur = (cur == 1) ? 2 : 1;
-                }
-                ctl.flags[8 * ctl.ncols + col] = (uint8_t)cur;
-            }
-        }
-    }
-    uint32_t *row = hist + ((size_t)col * RADIX + d) * ntiles;
-    uint32_t carry = 0;
-    for (int t0 = 0; t0 < ntiles; t0 += 64 * 4) {
-        uint32_t x[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                       // issue the loads together
-            const int t = t0 + j * 64 + lane;
-            x[j] = (t < ntiles) ? row[t] : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int t = t0 + j * 64 + lane;
-            uint32_t inc = x[j];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t y = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += y;
-            }
-            if (t < ntiles) row[t] = carry + inc - x[j];
-            carry += __shfl(inc, 63, 64);
-        }
-    }
-    if (lane == 0) tot[(size_t)col * RADIX + d] = carry;
-}
-
-template <bool FROM_F64, bool TO_F64>
-__global__ __launch_bounds__(SORT_THREADS) void scatter_kernel(
-    const void *__restrict__ src, int64_t src_ld, void *__restrict__ dst, int64_t dst_ld, int64_t n,
-    int shift, int ntiles, const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ digit_tot,
-    SkipCtl ctl)
-{
-    __shared__ uint32_t cnt[4][RADIX];
-    __shared__ uint32_t gdelta[RADIX];
-    __shared__ uint32_t wsum[8];
-    __shared__ uint64_t stage[SORT_TILE];
-    const int col = blockIdx.y, tile = blockIdx.x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int cur = ctl.flags ? ctl.flags[(shift >> 3) * ctl.ncols + col] : 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) cnt[w][threadIdx.x] = 0;
-    __syncthreads();
-    const char *csrc = reinterpret_cast<const char *>(src) + (size_t)col * src_ld * 8;
-    char *cdst = reinterpret_cast<char *>(dst) + (size_t)col * dst_ld * 8;
-    bool from_f64 = FROM_F64;
-    if (ctl.flags) {
-        if (cur == PASS_SKIPPED) return;                        // identity permutation: the keys stay put
-        from_f64 = cur == 0;
-        csrc = cur == 0 ? reinterpret_cast<const char *>(ctl.cols + (size_t)col * ctl.cols_ld)
-                        : reinterpret_cast<const char *>((cur == 1 ? ctl.buf_a : ctl.buf_b) + (size_t)col * n);
-        cdst = reinterpret_cast<char *>((cur == 1 ? ctl.buf_b : ctl.buf_a) + (size_t)col * n);
-    }
-    uint64_t keys[SORT_ITEMS];
-    uint32_t vm;
-    // one uniform branch around the sixteen loads (fp64 input after pass 0 only when every lower byte was constant)
-    if (FROM_F64 || from_f64) load_keys<true>(csrc, n, (int64_t)tile * SORT_TILE, keys, vm);
-    else load_keys<false>(csrc, n, (int64_t)tile * SORT_TILE, keys, vm);
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t rank[SORT_ITEMS];
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        const bool valid = (vm >> i) & 1u;
-        const uint32_t d = (uint32_t)(keys[i] >> shift) & 0xFF;
-        uint64_t peers = __ballot(valid);
-        // lanes holding the same digit: eight ballots -- unless the whole wavefront agrees (every
-        // constant digit position of an integer-valued column), which one shuffle + ballot detects
-        const uint32_t d0 = __shfl(d, peers ? __ffsll((long long)peers) - 1 : 0, 64);
-        if (__ballot(valid && d != d0) != 0) {
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) {
-                const bool set = (d >> bit) & 1u;
-                const uint64_t m = __ballot(set);
-                peers &= set ? m : ~m;
-            }
-        }
-        uint32_t r = 0;
-        if (valid) {
-            const uint32_t before = cnt[wave][d];
-            const uint32_t in_group = (uint32_t)__popcll(peers & lt_mask);
-            r = before + in_group;
-            __builtin_amdgcn_wave_barrier();
-            if (in_group == 0) cnt[wave][d] = before + (uint32_t)__popcll(peers);
-        }
-        __builtin_amdgcn_wave_barrier();
-        rank[i] = r;
-    }
-    __syncthreads();
-    // The keys are first placed in digit order in LDS (tile-local position = exclusive digit prefix
-    // + wave offset + rank), then written out by consecutive lanes: a digit's run of keys (16 on
-    // average) becomes one contiguous global store instead of 8-byte stores to 64 places.
-    {
-        const int d = threadIdx.x;
-        const uint32_t c0 = cnt[0][d], c1 = cnt[1][d], c2 = cnt[2][d], c3 = cnt[3][d];
-        const uint32_t total = c0 + c1 + c2 + c3;
-        // two exclusive prefixes over the 256 digits: the tile-local one (digit totals of this tile) and
-        // the global digit base (digit totals of the whole column, from scan_rows_kernel)
-        const uint32_t gtot = digit_tot[(size_t)col * RADIX + d];
-        uint32_t inc = total, ginc = gtot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(inc, off, 64), gy = __shfl_up(ginc, off, 64);
-            if (lane >= off) { inc += y; ginc += gy; }
-        }
-        if (lane == 63) { wsum[wave] = inc; wsum[4 + wave] = ginc; }
-        __syncthreads();
-        uint32_t lp = inc - total, gbase = ginc - gtot;
-        for (int w = 0; w < wave; ++w) { lp += wsum[w]; gbase += wsum[4 + w]; }
-        const uint32_t g = offsets[((size_t)col * RADIX + d) * ntiles + tile] + gbase;
-        gdelta[d] = g - lp;                                     // global position = gdelta[digit] + local position
-        cnt[0][d] = lp;
-        cnt[1][d] = lp + c0;
-        cnt[2][d] = lp + c0 + c1;
-        cnt[3][d] = lp + c0 + c1 + c2;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        if ((vm >> i) & 1u) {
-            const uint32_t d = (uint32_t)(keys[i] >> shift) & 0xFF;
-            stage[cnt[wave][d] + rank[i]] = keys[i];
-        }
-    }
-    __syncthreads();
-    const int64_t left = n - (int64_t)tile * SORT_TILE;
-    const int nv = (int)(left < SORT_TILE ? left : SORT_TILE);
-    for (int j = threadIdx.x; j < nv; j += SORT_THREADS) {
-        const uint64_t key = stage[j];
-        const uint32_t pos = gdelta[(uint32_t)(key >> shift) & 0xFF] + (uint32_t)j;
-        if (TO_F64) reinterpret_cast<double *>(cdst)[pos] = key_to_f64(key);
-        else reinterpret_cast<uint64_t *>(cdst)[pos] = key;
-    }
-}
-
-// scatter_kernel with a 32-bit payload travelling with every key (grx_kmeans.hip: the index of the value, so that the
-// sort also yields the permutation).  Single column, no pass skipping.  pay_src == nullptr: the payload is the
-// position (pass 0).  Stable like scatter_kernel: equal keys keep their index order.
-template <bool FROM_F64, bool TO_F64>
-__global__ __launch_bounds__(SORT_THREADS) void scatter_pairs_kernel(
-    const void *__restrict__ src, void *__restrict__ dst, const uint32_t *__restrict__ pay_src,
-    uint32_t *__restrict__ pay_dst, int64_t n, int shift, int ntiles, const uint32_t *__restrict__ offsets,
-    const uint32_t *__restrict__ digit_tot)
-{
-    __shared__ uint32_t cnt[4][RADIX];
-    __shared__ uint32_t gdelta[RADIX];
-    __shared__ uint32_t wsum[8];
-    __shared__ uint64_t stage[SORT_TILE];
-    __shared__ uint32_t stage_pay[SORT_TILE];
-    const int tile = blockIdx.x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) cnt[w][threadIdx.x] = 0;
-    __syncthreads();
-    uint64_t keys[SORT_ITEMS];
-    uint32_t pay[SORT_ITEMS];
-    uint32_t vm;
-    load_keys<FROM_F64>(src, n, (int64_t)tile * SORT_TILE, keys, vm);
-    {
-        const int64_t base = (int64_t)tile * SORT_TILE + (int64_t)wave * 64 * SORT_ITEMS + lane;
-        const int64_t last = n > 0 ? n - 1 : 0;
-#pragma unroll
-        for (int i = 0; i < SORT_ITEMS; ++i) {
-            const int64_t idx = base + (int64_t)i * 64;
-            pay[i] = pay_src ? pay_src[idx < n ? idx : last] : (uint32_t)idx;
-        }
-    }
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t rank[SORT_ITEMS];
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        const bool valid = (vm >> i) & 1u;
-        const uint32_t d = (uint32_t)(keys[i] >> shift) & 0xFF;
-        uint64_t peers = __ballot(valid);
-        const uint32_t d0 = __shfl(d, peers ? __ffsll((long long)peers) - 1 : 0, 64);
-        if (__ballot(valid && d != d0) != 0) {
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) {
-                const bool set = (d >> bit) & 1u;
-                const uint64_t m = __ballot(set);
-                peers &= set ? m : ~m;
-            }
-        }
-        uint32_t r = 0;
-        if (valid) {
-            const uint32_t before = cnt[wave][d];
-            const uint32_t in_group = (uint32_t)__popcll(peers & lt_mask);
-            r = before + in_group;
-            __builtin_amdgcn_wave_barrier();
-            if (in_group == 0) cnt[wave][d] = before + (uint32_t)__popcll(peers);
-        }
-        __builtin_amdgcn_wave_barrier();
-        rank[i] = r;
-    }
-    __syncthreads();
-    {
-        const int d = threadIdx.x;
-        const uint32_t c0 = cnt[0][d], c1 = cnt[1][d], c2 = cnt[2][d], c3 = cnt[3][d];
-        const uint32_t total = c0 + c1 + c2 + c3;
-        const uint32_t gtot = digit_tot[d];
-        uint32_t inc = total, ginc = gtot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(inc, off, 64), gy = __shfl_up(ginc, off, 64);
-            if (lane >= off) { inc += y; ginc += gy; }
-        }
-        if (lane == 63) { wsum[wave] = inc; wsum[4 + wave] = ginc; }
-        __syncthreads();
-        uint32_t lp = inc - total, gbase = ginc - gtot;
-        for (int w = 0; w < wave; ++w) { lp += wsum[w]; gbase += wsum[4 + w]; }
-        const uint32_t g = offsets[(size_t)d * ntiles + tile] + gbase;
-        gdelta[d] = g - lp;
-        cnt[0][d] = lp;
-        cnt[1][d] = lp + c0;
-        cnt[2][d] = lp + c0 + c1;
-        cnt[3][d] = lp + c0 + c1 + c2;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < SORT_ITEMS; ++i) {
-        if ((vm >> i) & 1u) {
-            const uint32_t d = (uint32_t)(keys[i] >> shift) & 0xFF;
-            const uint32_t at = cnt[wave][d] + rank[i];
-            stage[at] = keys[i];
-            stage_pay[at] = pay[i];
-        }
-    }
-    __syncthreads();
-    const int64_t left = n - (int64_t)tile * SORT_TILE;
-    const int nv = (int)(left < SORT_TILE ? left : SORT_TILE);
-    for (int j = threadIdx.x; j < nv; j += SORT_THREADS) {
-        const uint64_t key = stage[j];
-        const uint32_t pos = gdelta[(uint32_t)(key >> shift) & 0xFF] + (uint32_t)j;
-        if (TO_F64) reinterpret_cast<double *>(dst)[pos] = key_to_f64(key);
-        else reinterpret_cast<uint64_t *>(dst)[pos] = key;
-        pay_dst[pos] = stage_pay[j];
-    }
-}
-
-// One wavefront per column.  prune.py:33-54: repeat { size = max(int(frac*unbinned),1);
-// hi = value at sorted position done+size-1; extend to the end of hi's tie run }.
-__global__ __launch_bounds__(64) void bin_threshold_kernel(const double *__restrict__ sorted,
-                                                           int64_t ld, int64_t n, double frac,
-                                                           double *__restrict__ thr,
-                                                           int32_t *__restrict__ nbins, SkipCtl ctl)
-{
-    // with pass skipping the sorted column is wherever its last executed pass left it, as keys
-    // (buffer 0 = the input itself: every byte constant, i.e. all values equal)
-    const int where = ctl.flags ? ctl.flags[8 * ctl.ncols + blockIdx.x] : 0;
-    const double *sd = ctl.flags ? ctl.cols + (size_t)blockIdx.x * ctl.cols_ld : sorted + (size_t)blockIdx.x * ld;
-    const uint64_t *sk = (where == 1 ? ctl.buf_a : ctl.buf_b) + (size_t)blockIdx.x * n;
-    struct { const double *d; const uint64_t *k; bool keys;
-             __device__ double operator[](int64_t i) const { return keys ? key_to_f64(k[i]) : d[i]; } }
-        s{sd, sk, where != 0};
-    double *t = thr + (size_t)blockIdx.x * GRX_MAX_BINS;
-    const int lane = threadIdx.x;
-    int64_t done = 0;
-    int nb = 0;
-    while (done < n && nb < GRX_MAX_BINS) {
-        int64_t size = (int64_t)(frac * (double)(n - done));
-        if (size < 1) size = 1;
-        const int64_t pos = done + size - 1;
-        const double hi = s[pos];
-        int64_t L = pos + 1, R = n;
-        while (L < R) {
-            const int64_t len = R - L;
-            const int64_t step = (len + 63) >> 6;
-            const int64_t idx = L + (int64_t)lane * step;
-            const bool eq = (idx < R) && (s[idx] == hi);
-            const int c = __popcll(__ballot(eq));
-            if (c == 0) {
-                R = L;
-            } else {
-                const int64_t nL = L + (int64_t)(c - 1) * step + 1;
-                const int64_t cap = L + (int64_t)c * step;
-                R = (cap < R) ? cap : R;
-                L = nL;
-            }
-        }
-        if (lane == 0) t[nb] = hi;
-        ++nb;
-        done = L;
-    }
-    if (lane == 0) nbins[blockIdx.x] = nb;
-}
 
 // =======================================================================================
 // Binning-specific sort ("window" sort).  The threshold walk of prune.py:33-54 needs ~20 order
@@ -517,7 +72,7 @@ __global__ __launch_bounds__(256) void key_bits_kernel(const double *__restrict_
     uint32_t oi = 0, zi = 0, notint = 0;
     const int64_t last = n > 0 ? n - 1 : 0;
     for (int i0 = 0; i0 < 32; i0 += 8) {
-        // eight loads in flight (clamped addresses), then the conversions (see load_keys)
+        // eight loads in flight (clamped addresses), then the conversions (see load_keys, grx_sort.hip)
         double raw[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -631,7 +186,7 @@ __device__ __forceinline__ void load_keys2(const void *__restrict__ src, int src
     const int64_t last = n > 0 ? n - 1 : 0;
     valid_mask = 0;
     if (from_f64) {
-        // loads first, conversion behind a scheduling barrier (see load_keys)
+        // loads first, conversion behind a scheduling barrier (see load_keys, grx_sort.hip)
         double raw[SORT_ITEMS];
 #pragma unroll
         for (int i = 0; i < SORT_ITEMS; ++i) {
@@ -2071,143 +1626,9 @@ __global__ __launch_bounds__(256) void sel_assign_kernel(const double *__restric
     }
 }
 
-struct SortPlan {
-    int ntiles;
-    size_t keys_bytes;      // one key buffer: ncols * n * 8
-    size_t hist_bytes;      // ncols * RADIX * ntiles * 4
-};
-
-SortPlan make_plan(int64_t n, int ncols)
-{
-    SortPlan p;
-    p.ntiles = (int)grx_ceil_div(n, SORT_TILE);
-    p.keys_bytes = grx_align_up((size_t)ncols * (size_t)n * 8, 256);
-    // per-tile counters + digit totals + digit bases
-    p.hist_bytes = grx_align_up((size_t)ncols * RADIX * (size_t)p.ntiles * 4, 256) +
-                   2 * grx_align_up((size_t)ncols * RADIX * 4, 256);
-    return p;
-}
-
-// sort ncols columns; keysA/hist are scratch; result (fp64 ascending) in out (column stride out_ld)
-int sort_columns(int64_t n, int ncols, const double *cols, int64_t ld, double *out, int64_t out_ld,
-                 uint64_t *keysA, uint32_t *hist, hipStream_t st, SkipCtl ctl = SkipCtl{}, bool raw_u64 = false)
-{
-    const SortPlan p = make_plan(n, ncols);
-    const bool skipping = ctl.flags != nullptr;             // then out is a key buffer with stride n
-    const dim3 grid(p.ntiles, ncols);
-    uint32_t *tot = hist + grx_align_up((size_t)ncols * RADIX * (size_t)p.ntiles * 4, 256) / 4;
-    for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 8 * pass;
-        // ping-pong: pass 0 cols->A, odd A->out, even out->A; pass 7 writes fp64 into out
-        const void *src;
-        int64_t sld;
-        void *dst;
-        int64_t dld;
-        if (pass == 0) { src = cols; sld = ld; }
-        else if (pass & 1) { src = keysA; sld = n; }
-        else { src = out; sld = out_ld; }
-        if (pass & 1) { dst = out; dld = out_ld; }
-        else { dst = keysA; dld = n; }
-        {
-            GRX_PROF(GRX_K_SORT_COUNT, st);
-            if (pass == 0 && !raw_u64) tile_count_kernel<true><<<grid, SORT_THREADS, 0, st>>>(src, sld, n, shift, p.ntiles, hist, ctl);
-            else tile_count_kernel<false><<<grid, SORT_THREADS, 0, st>>>(src, sld, n, shift, p.ntiles, hist, ctl);
-        }
-        GRX_LAUNCH_CHECK();
-        {
-            GRX_PROF(GRX_K_SORT_SCAN, st);
-            scan_rows_kernel<<<dim3(RADIX, ncols), 64, 0, st>>>(hist, p.ntiles, tot, ctl, pass);
-        }
-        GRX_LAUNCH_CHECK();
-        {
-            GRX_PROF(GRX_K_SORT_SCATTER, st);
-            if (pass == 0 && !raw_u64) scatter_kernel<true, false><<<grid, SORT_THREADS, 0, st>>>(src, sld, dst, dld, n, shift, p.ntiles, hist, tot, ctl);
-            else if (pass == 7 && !skipping && !raw_u64) scatter_kernel<false, true><<<grid, SORT_THREADS, 0, st>>>(src, sld, dst, dld, n, shift, p.ntiles, hist, tot, ctl);
-            else scatter_kernel<false, false><<<grid, SORT_THREADS, 0, st>>>(src, sld, dst, dld, n, shift, p.ntiles, hist, tot, ctl);
-        }
-        GRX_LAUNCH_CHECK();
-    }
-    return GRX_OK;
-}
-
 }  // namespace
 
-// internal entry for other translation units (grx_quant.hip): workspace laid out as in
-// grx_sort_columns (key buffer, then counters)
-int grx_internal_sort_columns(int64_t n, int ncols, const double *cols, int64_t ld, double *out, int64_t out_ld,
-                              void *workspace, hipStream_t st)
-{
-    const SortPlan p = make_plan(n, ncols);
-    char *ws = reinterpret_cast<char *>(workspace);
-    return sort_columns(n, ncols, cols, ld, out, out_ld, reinterpret_cast<uint64_t *>(ws),
-                        reinterpret_cast<uint32_t *>(ws + p.keys_bytes), st);
-}
-
-// one fp64 column -> ascending values in `out` and, in `perm`, the index each sorted position came from (stable).
-// workspace: grx_sort_pairs_workspace_bytes(n) = key buffer, payload buffer, counters
-int grx_internal_sort_pairs(int64_t n, const double *col, double *out, uint32_t *perm, void *workspace, hipStream_t st)
-{
-    if (n <= 0) return GRX_OK;
-    const SortPlan p = make_plan(n, 1);
-    char *ws = reinterpret_cast<char *>(workspace);
-    uint64_t *keysA = reinterpret_cast<uint64_t *>(ws);
-    uint32_t *payA = reinterpret_cast<uint32_t *>(ws + p.keys_bytes);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(ws + p.keys_bytes + grx_align_up((size_t)n * 4, 256));
-    uint32_t *tot = hist + grx_align_up((size_t)RADIX * (size_t)p.ntiles * 4, 256) / 4;
-    const dim3 grid(p.ntiles, 1);
-    for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 8 * pass;
-        const void *src = pass == 0 ? (const void *)col : ((pass & 1) ? (const void *)keysA : (const void *)out);
-        void *dst = (pass & 1) ? (void *)out : (void *)keysA;
-        const uint32_t *psrc = pass == 0 ? nullptr : ((pass & 1) ? payA : perm);
-        uint32_t *pdst = (pass & 1) ? perm : payA;
-        {
-            GRX_PROF(GRX_K_SORT_COUNT, st);
-            if (pass == 0) tile_count_kernel<true><<<grid, SORT_THREADS, 0, st>>>(src, n, n, shift, p.ntiles, hist, SkipCtl{});
-            else tile_count_kernel<false><<<grid, SORT_THREADS, 0, st>>>(src, n, n, shift, p.ntiles, hist, SkipCtl{});
-        }
-        GRX_LAUNCH_CHECK();
-        {
-            GRX_PROF(GRX_K_SORT_SCAN, st);
-            scan_rows_kernel<<<dim3(RADIX, 1), 64, 0, st>>>(hist, p.ntiles, tot, SkipCtl{}, pass);
-        }
-        GRX_LAUNCH_CHECK();
-        {
-            GRX_PROF(GRX_K_SORT_SCATTER, st);
-            if (pass == 0) scatter_pairs_kernel<true, false><<<grid, SORT_THREADS, 0, st>>>(src, dst, psrc, pdst, n, shift, p.ntiles, hist, tot);
-            else if (pass == 7) scatter_pairs_kernel<false, true><<<grid, SORT_THREADS, 0, st>>>(src, dst, psrc, pdst, n, shift, p.ntiles, hist, tot);
-            else scatter_pairs_kernel<false, false><<<grid, SORT_THREADS, 0, st>>>(src, dst, psrc, pdst, n, shift, p.ntiles, hist, tot);
-        }
-        GRX_LAUNCH_CHECK();
-    }
-    return GRX_OK;
-}
-
-size_t grx_internal_sort_pairs_workspace_bytes(int64_t n)
-{
-    if (n <= 0) return 256;
-    const SortPlan p = make_plan(n, 1);
-    return p.keys_bytes + grx_align_up((size_t)n * 4, 256) + p.hist_bytes;
-}
-
-// raw 64-bit keys (graph ingest: (row, column) / (row, edge sequence) pairs), ascending; same workspace
-int grx_internal_sort_u64(int64_t n, const uint64_t *keys, uint64_t *out, void *workspace, hipStream_t st)
-{
-    if (n <= 0) return GRX_OK;
-    const SortPlan p = make_plan(n, 1);
-    char *ws = reinterpret_cast<char *>(workspace);
-    return sort_columns(n, 1, reinterpret_cast<const double *>(keys), n, reinterpret_cast<double *>(out), n,
-                        reinterpret_cast<uint64_t *>(ws), reinterpret_cast<uint32_t *>(ws + p.keys_bytes), st, SkipCtl{}, true);
-}
-
 extern "C" {
-
-size_t grx_sort_workspace_bytes(int64_t n, int ncols)
-{
-    if (n <= 0 || ncols <= 0) return 256;
-    const SortPlan p = make_plan(n, ncols);
-    return p.keys_bytes + p.hist_bytes;
-}
 
 namespace {
 struct SelLayout { size_t maps, luts, tieb, tiev, hist, cum, seg_off, cursor, bmax, tbroken, bmin, mark, idlist, nids, coll, bid, thr, thrb, nbins, fault, total; };
@@ -2245,43 +1666,13 @@ size_t grx_log_bin_workspace_bytes(int64_t n, int ncols)
 {
     if (n <= 0 || ncols <= 0) return 256;
     const SortPlan p = make_plan(n, ncols);
-    // keysA + sorted + hist + thresholds + nbins + pass-skipping state (key bits, flags)
+    // window sort: two key buffers + hist + thresholds + nbins + the per-tile key bits and the per-column plan
     const size_t sort_path = 2 * p.keys_bytes + p.hist_bytes + grx_align_up((size_t)ncols * GRX_MAX_BINS * 8, 256) +
                              grx_align_up((size_t)ncols * 4, 256) + grx_align_up((size_t)ncols * p.ntiles * 32, 256) +
                              grx_align_up((size_t)ncols * sizeof(BinPlanCol), 256);
     const size_t select_path = sel_layout(n, ncols).total;
     return sort_path > select_path ? sort_path : select_path;
 }
-
-int grx_sort_columns(int64_t n, int ncols, const double *d_cols, int64_t ld, double *d_sorted,
-                     int64_t ld_sorted, void *d_workspace, size_t workspace_bytes, void *stream)
-{
-    GRX_REQUIRE(n >= 0 && ncols >= 0 && ld >= n && ld_sorted >= n, "grx_sort_columns: bad shape");
-    GRX_REQUIRE(n < ((int64_t)1 << 31), "grx_sort_columns: n must be < 2^31");
-    if (n == 0 || ncols == 0) return GRX_OK;
-    GRX_REQUIRE(d_cols && d_sorted && d_workspace, "grx_sort_columns: NULL pointer");
-    if (workspace_bytes < grx_sort_workspace_bytes(n, ncols)) {
-        grx_set_error("grx_sort_columns: workspace %zu < %zu", workspace_bytes, grx_sort_workspace_bytes(n, ncols));
-        return GRX_ERR_WORKSPACE;
-    }
-    const SortPlan p = make_plan(n, ncols);
-    char *ws = reinterpret_cast<char *>(d_workspace);
-    return sort_columns(n, ncols, d_cols, ld, d_sorted, ld_sorted, reinterpret_cast<uint64_t *>(ws),
-                        reinterpret_cast<uint32_t *>(ws + p.keys_bytes), grx_stream(stream));
-}
-
-}  // extern "C"
-
-// Internal (grx_refex.hip): grx_vertical_log_bin_typed with an explicit place for the outcome flags -- d_status[0] (the
-// sort-free threshold walk met an unmarked bucket) and d_status[1] (a column needs more than GRX_MAX_BINS bins) are
-// set from inside the call's last kernel: no launch of its own, no synchronisation, the caller reads the two words
-// with whatever it copies back next.  (Round 4 passed the pointer through a thread-local that the next binning call of
-// the thread consumed -- a hidden coupling between two calls; gone.)
-int grx_internal_vertical_log_bin(int64_t n, int ncols, const double *d_cols, int64_t ld, const uint8_t *h_is_i64, double frac,
-                                  uint8_t *d_bins, int64_t ld_bins, int32_t *d_nbins, void *d_workspace,
-                                  size_t workspace_bytes, int32_t *d_status, void *stream);
-
-extern "C" {
 
 int grx_vertical_log_bin(int64_t n, int ncols, const double *d_cols, int64_t ld, double frac,
                          uint8_t *d_bins, int64_t ld_bins, int32_t *d_nbins, void *d_workspace,
@@ -2301,6 +1692,11 @@ int grx_vertical_log_bin_typed(int64_t n, int ncols, const double *d_cols, int64
 
 }  // extern "C"
 
+// Internal (grx_refex.hip): grx_vertical_log_bin_typed with an explicit place for the outcome flags -- d_status[0] (the
+// sort-free threshold walk met an unmarked bucket) and d_status[1] (a column needs more than GRX_MAX_BINS bins) are
+// set from inside the call's last kernel: no launch of its own, no synchronisation, the caller reads the two words
+// with whatever it copies back next.  (Round 4 passed the pointer through a thread-local that the next binning call of
+// the thread consumed -- a hidden coupling between two calls; gone.)
 int grx_internal_vertical_log_bin(int64_t n, int ncols, const double *d_cols, int64_t ld, const uint8_t *h_is_i64, double frac,
                                   uint8_t *d_bins, int64_t ld_bins, int32_t *d_nbins, void *d_workspace,
                                   size_t workspace_bytes, int32_t *status, void *stream)

@@ -6,7 +6,7 @@
 // so parity is by property: <= n_bins distinct output values, every value is
 // replaced by the mean of its cell, cells are nearest-centre cells, and the quantisation error is
 // not worse than sklearn's.  To meet the last point deterministically the start is not random:
-//   1. sort the values (batched radix sort of grx_prune.hip), prefix sums of s, s^2 and of
+//   1. sort the values (batched radix sort of grx_sort.hip), prefix sums of s, s^2 and of
 //      cbrt(gap)^2 (Panter-Dite: optimal cell density ~ pdf^(1/3))
 //   2. cut the sorted values into <= 1024 micro-cells of equal cbrt-density mass (or one value per
 //      cell when there are few values) and solve the k-cluster problem on the cells EXACTLY by
@@ -16,10 +16,6 @@
 //   4. map every input value to its cell centre.
 // With <= 1024 values step 2 is the exact optimum of the k-means objective (<= any k-means run).
 #include "grx_common.h"
-
-int grx_internal_sort_columns(int64_t n, int ncols, const double *cols, int64_t ld, double *out, int64_t out_ld,
-                              void *workspace, hipStream_t st);
-extern "C" size_t grx_sort_workspace_bytes(int64_t n, int ncols);
 
 namespace {
 

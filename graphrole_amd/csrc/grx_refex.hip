@@ -19,11 +19,6 @@
 #include <string>
 #include <vector>
 
-int64_t grx_internal_plan_max_degree(const grx_aggregate_plan *plan);                                          // grx_graph.hip
-int grx_internal_vertical_log_bin(int64_t n, int ncols, const double *d_cols, int64_t ld, const uint8_t *h_is_i64, double frac,
-                                  uint8_t *d_bins, int64_t ld_bins, int32_t *d_nbins, void *d_workspace,
-                                  size_t workspace_bytes, int32_t *d_status, void *stream);                  // grx_prune.hip
-
 namespace {
 
 const char *const AGG_NAMES[] = {"sum", "mean", "min", "max", "var", "std", "prod", "median", "count", "size"};

@@ -81,6 +81,23 @@ def test_argument_validation_needs_no_device():
     assert lib.grx_nmf_workspace_bytes(1_000_000, 20, 6) > 0
 
 
+def test_sort_and_log_bin_workspace_sizes_are_pinned():
+    """The two workspace queries are ABI: callers size arenas with them.  The values are those of the commit before
+    the radix sort moved out of grx_prune.hip into grx_sort.hip (default GRX_BIN_BID_MIN_N)."""
+    from graphrole_amd import _lib
+    lib = _lib.load()
+    pinned = {
+        (1, 1): (3328, 175616),
+        (4096, 1): (35840, 208128),
+        (4097, 3): (110848, 622592),
+        (1_000_000, 12): (99035136, 195142144),
+        (2_500_000, 2): (41255424, 81297152),
+    }
+    for (n, ncols), (sort_bytes, log_bin_bytes) in pinned.items():
+        assert lib.grx_sort_workspace_bytes(n, ncols) == sort_bytes, (n, ncols)
+        assert lib.grx_log_bin_workspace_bytes(n, ncols) == log_bin_bytes, (n, ncols)
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

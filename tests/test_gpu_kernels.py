@@ -994,3 +994,21 @@ def test_log_bin_stored_bucket_id_path_equals_the_default():
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     assert ' passed' in res.stdout
 
+
+def test_grx_bin_sort_switch_gives_the_oracle_bins():
+    """GRX_BIN_SORT=1 bins through the window sort (key_bits -> bin_plan -> four rounds of tile_count2 / scan_rows2 /
+    scatter2 -> bin_threshold2, csrc/grx_prune.hip) instead of the default sort-free selection; grx_refex_run's error
+    text sends users there.  The switch is read once per process, so a fresh child runs the cases written for that path
+    -- the reference's known answers, every pattern of constant / varying key bytes, the NARROW / WIDE / integer-key
+    columns and their unresolved runs -- against the oracle (bins are integers: equal, not close)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GRX_BIN_SORT='1')
+    res = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(root, 'tests', 'test_gpu_kernels.py'), '-q', '-m', 'gpu', '-x',
+                          '-k', 'test_log_bin_reference_known_answers or test_log_bin_pass_skipping_patterns or '
+                                'test_log_bin_window_sort_adversarial', '-p', 'no:cacheprovider'],
+                         capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
+    assert '6 passed' in res.stdout
+
