@@ -251,6 +251,9 @@ _SIGNATURES = {
     'grx_distance_sums_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
     'grx_distance_sums': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'grx_eccentricity_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
+    'grx_eccentricity': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'grx_biconnected_workspace_bytes': (c_size_t, [c_int64]),
     'grx_biconnected': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int64), c_void_p, c_size_t, c_void_p]),

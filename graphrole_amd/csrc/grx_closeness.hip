@@ -21,6 +21,8 @@
 // At the end harmonic(v) = harm(v) 2^-84, rounded once to nearest-even: the correctly rounded sum of the fp64
 // terms fl(1 / d), the same bits for every W, source order and run.  Integer arithmetic only; no floating-point
 // atomics (the source bits are set with integer atomicOr).
+// grx_eccentricity (below grx_distance_sums' kernels) runs the same BFS with a maximum in place of the sums: the
+// eccentricity of every source, the per-target maximum distance and the eccentricity bounds of Takes and Kosters.
 #pragma clang fp contract(off)
 
 #include "grx_common.h"
@@ -305,6 +307,267 @@ int run(const Args &a, const ClWs &ws, hipStream_t st)
     return GRX_OK;
 }
 
+// ---- eccentricities (grx_eccentricity) ---------------------------------------------------------------------------
+// The same bitset BFS with an extremal reduction in place of the sums.  Pass A of a batch: reach(v) += c,
+// lower(v) = max(lower(v), d) for the level d at which new source bits arrive at v, and ecc(b) = the last level at which
+// bit b was newly set anywhere (every workgroup ORs its `next` words through LDS and one lane per set bit stores d into
+// the batch's int32 slots: many workgroups store the same value in one launch, plain stores).  Pass B, with the upper
+// bounds asked for, replays the batch with ecc(b) now known (staged in LDS) and tightens the bounds of Takes and
+// Kosters (2013): for the new bits nw of v at level d (level 0: the source itself)
+//   upper(v) = min(upper(v), d + min over nw of ecc(b)),  lower(v) = max(lower(v), max over nw of ecc(b) - d),
+// valid where d(s, v) = d(v, s): a symmetric CSR.  A source's own level-0 update pins lower = upper = ecc there.
+
+constexpr int EC_WAVES = CL_BLOCK / GRX_WAVE;
+
+size_t ec_ws_bytes(int64_t n, int W)
+{
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    return 3 * grx_align_up(nn * (size_t)W * 8, 256) + 256;
+}
+
+ClWs ec_carve(void *base, int64_t n, int W)
+{
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    char *p = reinterpret_cast<char *>(base);
+    ClWs ws;
+    ws.visited = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
+    ws.f0 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
+    ws.f1 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
+    ws.harm = nullptr;
+    ws.ctrl = reinterpret_cast<int32_t *>(p);
+    return ws;
+}
+
+// min resp. max over the W lanes of a group (every lane of the wavefront takes part)
+template <int W>
+__device__ __forceinline__ void group_min_max(int &lo, int &hi)
+{
+#pragma unroll
+    for (int off = 1; off < W; off <<= 1) {
+        lo = min(lo, __shfl_xor(lo, off, W));
+        hi = max(hi, __shfl_xor(hi, off, W));
+    }
+}
+
+// (min, max) of ecc over the set bits of word w's new bits; (INT32_MAX, -1) for none
+__device__ __forceinline__ void ecc_range(uint64_t nw, const int32_t *ecc_w, int &lo, int &hi)
+{
+    lo = INT32_MAX;
+    hi = -1;
+    for (uint64_t m = nw; m; m &= m - 1) {
+        const int e = ecc_w[__builtin_ctzll(m)];
+        lo = min(lo, e);
+        hi = max(hi, e);
+    }
+}
+
+// pass B, level 0: source lane b sits on s_b at distance 0 (integer atomics: one node may carry several lanes)
+__global__ __launch_bounds__(CL_BLOCK) void ec_source_bounds_kernel(int64_t n, int count,
+                                                                    const int32_t *__restrict__ src,
+                                                                    const int32_t *__restrict__ secc,
+                                                                    int32_t *__restrict__ lower,
+                                                                    int32_t *__restrict__ upper)
+{
+    for (int b = blockIdx.x * CL_BLOCK + threadIdx.x; b < count; b += gridDim.x * CL_BLOCK) {
+        const int64_t s = src[b];
+        if (s < 0 || s >= n) continue;
+        atomicMin(&upper[s], secc[b]);
+        atomicMax(&lower[s], secc[b]);
+    }
+}
+
+// one level, rows up to hub_degree arcs (the shape of cl_level_kernel).  secc: the batch's int32[count] slots of the
+// source eccentricities, written by pass A (BOUNDS = false) and read by pass B
+template <int W, bool BOUNDS>
+__global__ __launch_bounds__(CL_BLOCK) void ec_level_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+                                                            const int32_t *__restrict__ col, int64_t hub_degree,
+                                                            int count, uint64_t *__restrict__ visited,
+                                                            uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
+                                                            int32_t *__restrict__ secc, int64_t *__restrict__ reach,
+                                                            int32_t *__restrict__ lower, int32_t *__restrict__ upper,
+                                                            int32_t *__restrict__ ctrl)
+{
+    constexpr int GROUPS = CL_BLOCK / W;
+    __shared__ int32_t ecc[BOUNDS ? GRX_WAVE * W : 1];
+    __shared__ uint64_t seen_of[BOUNDS ? 1 : EC_WAVES][W];
+    if (ctrl[GRX_CT_DONE]) return;                          // the same in every lane of the launch
+    const int l = ctrl[GRX_CT_LEVEL], d = l + 1;
+    const uint64_t *F = (l & 1) ? f1 : f0;
+    uint64_t *Fn = (l & 1) ? f0 : f1;
+    const int w = threadIdx.x % W;
+    const uint64_t active = active_mask(count, w);
+    if constexpr (BOUNDS) {
+        for (int b = threadIdx.x; b < GRX_WAVE * W; b += CL_BLOCK) ecc[b] = b < count ? secc[b] : 0;
+        __syncthreads();
+    }
+    int found = 0;
+    uint64_t seen = 0;
+    // the trip count is the same in every lane of the workgroup: the group reductions below see every lane
+    for (int64_t first = (int64_t)blockIdx.x * GROUPS; first < n; first += (int64_t)gridDim.x * GROUPS) {
+        const int64_t v = first + threadIdx.x / W;
+        bool mine = false;
+        uint64_t nw = 0;
+        if (v < n) {
+            const int64_t b = row_ptr[v], e = row_ptr[v + 1];
+            if (e - b <= hub_degree) {                      // longer rows: ec_level_hub_kernel
+                mine = true;
+                const int64_t cell = v * W + w;
+                const uint64_t vw = visited[cell];
+                nw = pull_words<W>(b, e, 1, col, F, w, active & ~vw);
+                Fn[cell] = nw;
+                if (nw) visited[cell] = vw | nw;
+            }
+        }
+        if constexpr (BOUNDS) {
+            int lo, hi;
+            ecc_range(nw, ecc + w * GRX_WAVE, lo, hi);
+            group_min_max<W>(lo, hi);
+            if (mine && w == 0 && hi >= 0) {
+                upper[v] = min(upper[v], d + lo);
+                lower[v] = max(lower[v], hi - d);
+                found = 1;
+            }
+        } else {
+            seen |= nw;
+            const int c = group_sum<W>(__popcll(nw));
+            if (mine && w == 0 && c) {
+                reach[v] += c;
+                lower[v] = max(lower[v], d);
+                found = 1;
+            }
+        }
+    }
+    if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[GRX_CT_FOUND] = 1;
+    if constexpr (!BOUNDS) {
+        // OR over the lanes of the wavefront that hold word w, then over the wavefronts through LDS
+#pragma unroll
+        for (int off = W; off < GRX_WAVE; off <<= 1)
+            seen |= __shfl_xor((unsigned long long)seen, off, GRX_WAVE);
+        if (threadIdx.x % GRX_WAVE < W) seen_of[threadIdx.x / GRX_WAVE][w] = seen;
+        __syncthreads();
+        for (int b = threadIdx.x; b < GRX_WAVE * W; b += CL_BLOCK) {
+            uint64_t m = 0;
+#pragma unroll
+            for (int k = 0; k < EC_WAVES; ++k) m |= seen_of[k][b / GRX_WAVE];
+            if ((m >> (b % GRX_WAVE)) & 1) secc[b] = d;     // set bits lie below `count`
+        }
+    }
+}
+
+// one level, hub rows (the shape of cl_level_hub_kernel)
+template <int W, bool BOUNDS>
+__global__ __launch_bounds__(CL_BLOCK) void ec_level_hub_kernel(const int64_t *__restrict__ row_ptr,
+                                                                const int32_t *__restrict__ col,
+                                                                const int32_t *__restrict__ hub_rows, int count,
+                                                                uint64_t *__restrict__ visited,
+                                                                uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
+                                                                int32_t *__restrict__ secc,
+                                                                int64_t *__restrict__ reach,
+                                                                int32_t *__restrict__ lower,
+                                                                int32_t *__restrict__ upper,
+                                                                int32_t *__restrict__ ctrl)
+{
+    constexpr int GROUPS = CL_BLOCK / W;
+    __shared__ uint64_t part[CL_BLOCK];
+    if (ctrl[GRX_CT_DONE]) return;
+    const int l = ctrl[GRX_CT_LEVEL], d = l + 1;
+    const uint64_t *F = (l & 1) ? f1 : f0;
+    uint64_t *Fn = (l & 1) ? f0 : f1;
+    const int t = threadIdx.x, w = t % W;
+    const int64_t v = hub_rows[blockIdx.x];
+    const int64_t cell = v * W + w;
+    const uint64_t vw = visited[cell];
+    part[t] = pull_words<W>(row_ptr[v] + t / W, row_ptr[v + 1], GROUPS, col, F, w, active_mask(count, w) & ~vw);
+    __syncthreads();
+#pragma unroll
+    for (int s = CL_BLOCK / 2; s >= W; s >>= 1) {          // part[t] for t < W: the OR over every group
+        if (t < s) part[t] |= part[t + s];
+        __syncthreads();
+    }
+    if constexpr (!BOUNDS) {
+        for (int b = t; b < GRX_WAVE * W; b += CL_BLOCK)
+            if ((part[b / GRX_WAVE] >> (b % GRX_WAVE)) & 1) secc[b] = d;
+    }
+    if (t >= GRX_WAVE) return;
+    const uint64_t nw = t < W ? part[t] : 0;
+    if (t < W) {
+        Fn[cell] = nw;
+        if (nw) visited[cell] = vw | nw;
+    }
+    if constexpr (BOUNDS) {
+        int lo, hi;
+        ecc_range(nw, secc + w * GRX_WAVE, lo, hi);         // a few rows: straight from global memory
+        group_min_max<W>(lo, hi);
+        if (t == 0 && hi >= 0) {
+            upper[v] = min(upper[v], d + lo);
+            lower[v] = max(lower[v], hi - d);
+            ctrl[GRX_CT_FOUND] = 1;
+        }
+    } else {
+        const int c = group_sum<W>(__popcll(nw));
+        if (t == 0 && c) {
+            reach[v] += c;
+            lower[v] = max(lower[v], d);
+            ctrl[GRX_CT_FOUND] = 1;
+        }
+    }
+}
+
+struct EcArgs {
+    int64_t n;
+    const int64_t *row_ptr;
+    const int32_t *col;
+    const int32_t *hub_rows;
+    int64_t n_hub_rows, hub_degree;
+    const int32_t *sources;
+    int64_t n_sources;
+    int32_t *source_ecc;
+    int64_t *reach;
+    int32_t *lower, *upper;
+};
+
+// one BFS of the batch [first, first + count): pass A, or pass B over the same sources
+template <int W, bool BOUNDS>
+int ec_bfs(const EcArgs &a, const ClWs &ws, int64_t first, int count, hipStream_t st)
+{
+    const int64_t n = a.n;
+    const unsigned row_blocks = grx_grid(n, CL_BLOCK / W, CL_MAX_ROW_BLOCKS);
+    int32_t *secc = a.source_ecc + first;
+    grx_fill64(ws.visited, n * W, 0, st);
+    grx_fill64(ws.f0, n * W, 0, st);
+    cl_source_init_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
+        n, W, count, a.sources + first, ws.visited, ws.f0, ws.ctrl);
+    if (BOUNDS)
+        ec_source_bounds_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
+            n, count, a.sources + first, secc, a.lower, a.upper);
+    GRX_LAUNCH_CHECK();
+    int32_t h[2];
+    // a BFS has at most n - 1 levels; one more launch finds the empty frontier
+    return grx_run_rounds(
+        "grx_eccentricity: the BFS did not end after %lld levels", CL_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
+            if (a.n_hub_rows)
+                ec_level_hub_kernel<W, BOUNDS><<<(unsigned)a.n_hub_rows, CL_BLOCK, 0, st>>>(
+                    a.row_ptr, a.col, a.hub_rows, count, ws.visited, ws.f0, ws.f1, secc, a.reach, a.lower, a.upper,
+                    ws.ctrl);
+            ec_level_kernel<W, BOUNDS><<<row_blocks, CL_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.hub_degree, count,
+                                                                        ws.visited, ws.f0, ws.f1, secc, a.reach,
+                                                                        a.lower, a.upper, ws.ctrl);
+            return grx_frontier_advance(ws.ctrl, st);
+        });
+}
+
+template <int W>
+int ec_run(const EcArgs &a, const ClWs &ws, hipStream_t st)
+{
+    for (int64_t first = 0; first < a.n_sources; first += 64 * W) {
+        const int count = (int)std::min<int64_t>(64 * W, a.n_sources - first);
+        int rc = ec_bfs<W, false>(a, ws, first, count, st);
+        if (rc == GRX_OK && a.upper) rc = ec_bfs<W, true>(a, ws, first, count, st);
+        if (rc != GRX_OK) return rc;
+    }
+    return GRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -345,6 +608,49 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
     case 4: return run<4>(a, ws, st);
     case 8: return run<8>(a, ws, st);
     default: return run<16>(a, ws, st);
+    }
+}
+
+size_t grx_eccentricity_workspace_bytes(int64_t n, int words, int64_t n_sources)
+{
+    return ec_ws_bytes(n, choose_words(n, words, n_sources));
+}
+
+int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                     int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
+                     int32_t *d_source_ecc, int64_t *d_reach, int32_t *d_lower, int32_t *d_upper, int accumulate,
+                     void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_eccentricity: n = %lld out of range", (long long)n);
+    GRX_REQUIRE(d_row_ptr && d_col && d_reach && d_lower && d_workspace, "grx_eccentricity: null pointer");
+    GRX_REQUIRE(n_sources >= 0 && n_sources < (int64_t)1 << 31 && (n_sources == 0 || (d_sources && d_source_ecc)),
+                "grx_eccentricity: source list");
+    GRX_REQUIRE(words == 0 || valid_words(words), "grx_eccentricity: words must be 0, 1, 2, 4, 8 or 16 (got %d)",
+                words);
+    GRX_REQUIRE(lanes_per_row >= 1, "grx_eccentricity: lanes_per_row must be >= 1");
+    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows), "grx_eccentricity: hub list");
+    GRX_REQUIRE(accumulate == 0 || accumulate == 1, "grx_eccentricity: accumulate must be 0 or 1 (got %d)",
+                accumulate);
+    const int W = choose_words(n, words, n_sources);
+    GRX_REQUIRE(workspace_bytes >= ec_ws_bytes(n, W), "grx_eccentricity: workspace %zu bytes, need %zu",
+                workspace_bytes, ec_ws_bytes(n, W));
+    hipStream_t st = grx_stream(stream);
+    const ClWs ws = ec_carve(d_workspace, n, W);
+    const EcArgs a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
+                   d_sources, n_sources, d_source_ecc, d_reach, d_lower, d_upper};
+    if (!accumulate) {
+        grx_fill64(reinterpret_cast<uint64_t *>(d_reach), n, 0, st);
+        grx_fill32(d_lower, n, 0, st);
+        if (d_upper) grx_fill32(d_upper, n, INT32_MAX, st);
+    }
+    if (n_sources) grx_fill32(d_source_ecc, n_sources, 0, st);
+    GRX_LAUNCH_CHECK();
+    switch (W) {
+    case 1: return ec_run<1>(a, ws, st);
+    case 2: return ec_run<2>(a, ws, st);
+    case 4: return ec_run<4>(a, ws, st);
+    case 8: return ec_run<8>(a, ws, st);
+    default: return ec_run<16>(a, ws, st);
     }
 }
 

@@ -1271,6 +1271,31 @@ def distance_sums(csr_pull: DeviceCSR, sources: np.ndarray,
     return reach, dsum, harmonic
 
 
+def eccentricity_pass(csr_pull: DeviceCSR, sources: np.ndarray, words: int = 0, bounds=None,
+                      want_upper: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                         Optional[torch.Tensor]]:
+    """grx_eccentricity: (source_ecc int32[len(sources)], reach int64[n], lower int32[n], upper int32[n] or None) of
+    the BFS from `sources` (internal row ids) pulled over csr_pull, as ``distance_sums`` pulls.  bounds=None: the call
+    initialises lower = 0 and, with want_upper, upper = INT32_MAX; without want_upper there is no upper and no second
+    pass (lower is then the per-target maximum distance only).  bounds=(lower, upper): int32 device tensors carried
+    over from an earlier call and updated in place (upper may be None); reach counts this call's sources alone.
+    The bounds hold on a symmetric csr_pull only (an undirected graph)."""
+    n = csr_pull.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    ws, ws_bytes = _workspace('grx_eccentricity_workspace_bytes', n, int(words), len(src))   # for the W the call uses
+    source_ecc = torch.empty(max(len(src), 1), dtype=torch.int32, device=device())
+    if bounds is None:
+        reach = torch.empty(max(n, 1), dtype=torch.int64, device=device())
+        lower = torch.empty(max(n, 1), dtype=torch.int32, device=device())
+        upper = torch.empty(max(n, 1), dtype=torch.int32, device=device()) if want_upper else None
+    else:
+        lower, upper = bounds
+        reach = zeros(max(n, 1), dtype=torch.int64)
+    _lib.call('grx_eccentricity', n, *_csr_args(csr_pull), _ptr(src), len(src), int(words), _ptr(source_ecc),
+              _ptr(reach), _ptr(lower), _ptr(upper), int(bounds is not None), _ptr(ws), ws_bytes, _stream())
+    return source_ecc[:len(src)], reach, lower, upper
+
+
 def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor],
                                                                     Optional[torch.Tensor], int]:
     """grx_biconnected on the symmetric CSR of an undirected graph's distinct arcs: (count int64[n] = the number of

@@ -8,7 +8,9 @@ csrc/grx_measures.hip, betweenness centrality (opt-in: O(n m)) by the batched Br
 csrc/grx_betweenness.hip, and closeness and harmonic centrality (opt-in: O(n m)) from the per-target distance sums of
 the bitset multi-source BFS of csrc/grx_closeness.hip, the number of biconnected components of every node (opt-in;
 more than one: an articulation point) by the Tarjan-Vishkin sweeps of csrc/grx_biconnected.hip, and the core number
-and onion layer of every node (opt-in) by the synchronous peeling of csrc/grx_kcore.hip.
+and onion layer of every node (opt-in) by the synchronous peeling of csrc/grx_kcore.hip, and the eccentricity of every
+node (opt-in) -- with it diameter, radius, center and periphery -- by the extremal passes of the same multi-source
+BFS (grx_eccentricity in csrc/grx_closeness.hip).
 """
 from __future__ import annotations
 
@@ -38,13 +40,15 @@ CATALOGUE = {
     'biconnected_components': 'Counter(v for c in nx.biconnected_components(G) for v in c)',
     'core_number': 'nx.core_number(G)',
     'onion_layer': 'nx.onion_layers(G)',
+    'eccentricity': 'nx.eccentricity(G)',
 }
 
 #: catalogue entries computed only when named: not in ``available_measures`` nor in the default table -- the
-#: centralities because they cost O(n m), 'biconnected_components', 'core_number' and 'onion_layer' (O(n + m)) because
-#: the default table and ``available_measures`` are pinned as they were before they existed
+#: centralities and 'eccentricity' because they cost up to O(n m), 'biconnected_components', 'core_number' and
+#: 'onion_layer' (O(n + m)) because the default table and ``available_measures`` are pinned as they were before they
+#: existed
 OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality', 'biconnected_components',
-          'core_number', 'onion_layer')
+          'core_number', 'onion_layer', 'eccentricity')
 
 
 def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
@@ -121,6 +125,7 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       ``'onion_layer'`` of a multigraph or of a graph with a self-loop), or that is outside this implementation's scope
       (directed / multigraph clustering and effective size)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
+    :raises networkx.NetworkXError: ``'eccentricity'`` of a graph that is not (strongly) connected, as networkx
 
     Stated divergence: ``effective_size`` of a node whose only neighbour is itself is NaN (networkx raises
     ZeroDivisionError).
@@ -224,6 +229,10 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col, dt = peeling()[0], np.dtype('int64')
         elif nm == 'onion_layer':
             col, dt = peeling()[1], np.dtype('int64')
+        elif nm == 'eccentricity':
+            if 'eccentricity' not in cache:                   # its own kernel: not one of the sums of distances()
+                cache['eccentricity'] = _eccentricity_column(graph, K, 'all')[0]
+            col, dt = cache['eccentricity'], np.dtype('int64')
         elif nm == 'pagerank':
             col, iterations[nm] = K.pagerank(tr if directed else out, K.row_sums(out, False), alpha, tol, max_iter)
             dt = np.dtype('float64')
@@ -346,9 +355,9 @@ def _closeness(reach: np.ndarray, dsum: np.ndarray, n: int, wf_improved: bool) -
     return c
 
 
-def _distance_arguments(name: str, distance) -> None:
+def _distance_arguments(name: str, distance, keyword: str = 'distance') -> None:
     if distance is not None:
-        raise NotImplementedError(f'weighted distances (nx.{name}(G, distance={distance!r})) need a shortest-path '
+        raise NotImplementedError(f'weighted distances (nx.{name}(G, {keyword}={distance!r})) need a shortest-path '
                                   f'search by weight and are not implemented here; use networkx')
 
 
@@ -548,3 +557,216 @@ def onion_layers(G) -> pd.Series:
       for none of them (its own limits, not divergences)
     """
     return node_measures(G, ['onion_layer'])['onion_layer']
+
+
+# ------------------------------------------------------------------------------------------------- eccentricity
+#: source words of one round of the bounds method when the caller leaves `words` to the library (64 sources per word)
+_ECC_BOUNDS_WORDS = 16
+_ECC_INF = int(np.iinfo(np.int32).max)
+
+
+def _row_lengths(csr) -> np.ndarray:
+    """Arcs per row of a device CSR, from its host row pointers."""
+    host = getattr(csr, '_host', None)                          # kernels.DeviceCSR keeps its row pointers on the host
+    return np.diff(np.asarray(csr.row_ptr if host is None else host[0], dtype=np.int64))
+
+
+def _label_index(graph) -> pd.Index:
+    """The index of ``_frame``: the sorted node labels."""
+    csr = graph.to_csr()
+    return csr.label_index() if hasattr(csr, 'label_index') else pd.Index(graph._device_graph()[0].labels)
+
+
+def _require_full_reach(K, reach, sources: np.ndarray, n: int, directed: bool) -> None:
+    """networkx's ``len(shortest_path_length(G, s)) != len(G)`` for every source s at once: node v is reached by every
+    source iff reach[v] + [v is a source] equals the number of sources."""
+    got = np.asarray(K.to_host(reach))[:n].astype(np.int64) + np.bincount(sources, minlength=n)
+    if np.any(got != len(sources)):
+        import networkx as nx
+        raise nx.NetworkXError('Found infinite path length because the digraph is not strongly connected' if directed
+                               else 'Found infinite path length because the graph is not connected')
+
+
+def _eccentricity_of_rows(graph, K, sources: np.ndarray, words: int):
+    """method='all': one BFS per source (internal row ids) along the out-arcs, pass A only; the device int32 tensor of
+    their eccentricities, in the order of `sources`."""
+    if graph.directed:
+        pull = _structure_pair(graph, 'eccentricity')[1]        # walking out-arcs = pulling over the in-adjacency
+    else:
+        pull = graph._structure_csrs()[0]
+    ecc, reach, _, _ = K.eccentricity_pass(pull, sources, words)
+    _require_full_reach(K, reach, sources, pull.n, bool(graph.directed))
+    return ecc
+
+
+def _select_sources(lower: np.ndarray, upper: np.ndarray, open_rows: np.ndarray, rank: np.ndarray,
+                    batch: int) -> np.ndarray:
+    """The sources of one round of the bounds method among the unresolved rows: half of the batch the rows with the
+    largest upper bound, the other half the rows with the smallest lower bound (Takes and Kosters' interchanging
+    rule, a batch at a time); ties by `rank` (larger degree, then smaller row).  Ascending row ids."""
+    if len(open_rows) <= batch:
+        return open_rows
+    n_hi = batch // 2
+    key = (upper[open_rows] << 31) | (len(rank) - 1 - rank[open_rows])     # distinct keys: the set is determined
+    taken = np.argpartition(key, len(key) - n_hi)[len(key) - n_hi:]
+    left = np.ones(len(open_rows), dtype=bool)
+    left[taken] = False
+    hi, rest = open_rows[taken], open_rows[left]
+    key = (lower[rest] << 31) | rank[rest]
+    lo = rest[np.argpartition(key, batch - n_hi - 1)[:batch - n_hi]]
+    return np.sort(np.concatenate([hi, lo]))
+
+
+def _eccentricity_by_bounds(graph, K, words: int):
+    """method='bounds' on an undirected graph: rounds of up to 64 W sources, each one BFS pass for the sources' own
+    eccentricities and a second one that tightens every node's bounds with them, until lower = upper everywhere.
+    (device int32 tensor of the eccentricities in internal row order, rounds, sources used)."""
+    csr = graph._structure_csrs()[0]
+    n = csr.n
+    batch = 64 * (int(words) or _ECC_BOUNDS_WORDS)
+    deg = _row_lengths(csr)
+    rank = np.empty(n, dtype=np.int64)
+    rank[np.lexsort((np.arange(n), -deg))] = np.arange(n)
+    lower = np.zeros(n, dtype=np.int64)
+    upper = np.full(n, _ECC_INF, dtype=np.int64)
+    bounds = None
+    rounds = used = 0
+    while True:
+        open_rows = np.nonzero(lower < upper)[0]
+        if not len(open_rows):
+            return bounds[0], rounds, used
+        if rounds * batch >= n:                                 # every round resolves at least its own sources
+            raise RuntimeError(f'eccentricity bounds did not close after {rounds} rounds of {batch} sources')
+        sources = _select_sources(lower, upper, open_rows, rank, batch)
+        if bounds is None:
+            _, reach, lo, up = K.eccentricity_pass(csr, sources, words, want_upper=True)
+            _require_full_reach(K, reach, sources, n, False)    # any one source decides: the graph is undirected
+        else:
+            _, _, lo, up = K.eccentricity_pass(csr, sources, words, bounds=bounds)
+        bounds = (lo, up)
+        lower = np.asarray(K.to_host(lo))[:n].astype(np.int64)
+        upper = np.asarray(K.to_host(up))[:n].astype(np.int64)
+        rounds += 1
+        used += len(sources)
+
+
+def _eccentricity_column(graph, K, method: str, words: int = 0):
+    """The eccentricity of every node as a device column in internal row order, and how it was computed:
+    (column, {'method', 'rounds', 'sources'})."""
+    n = graph._device_graph()[0].n
+    if method == 'bounds' and not graph.directed:
+        col, rounds, used = _eccentricity_by_bounds(graph, K, words)
+        return col, {'method': 'bounds', 'rounds': rounds, 'sources': used}
+    col = _eccentricity_of_rows(graph, K, np.arange(n, dtype=np.int64), words)
+    return col, {'method': 'all', 'rounds': 1, 'sources': n}
+
+
+def eccentricity(G, v=None, method: str = 'all', weight=None, words: int = 0):
+    """
+    Eccentricity on the GPU -- the largest distance from a node to any other node, which separates the periphery of a
+    network from its centre: ``nx.eccentricity(G, v)`` of networkx 3.4.2 (distance_measures.py) by grx_eccentricity
+    (csrc/grx_closeness.hip), the bitset multi-source BFS of the closeness kernels with a maximum in place of the sums.
+
+    :param G: any graph ``node_measures`` accepts; multigraph edges count once and self-loops are ignored (as in
+      networkx, where neither changes a distance)
+    :param v: None = every node; a node = that node only; otherwise the members of the iterable that are nodes
+      (networkx's ``G.nbunch_iter``)
+    :param method: ``'all'`` (the default) runs one BFS per requested node, up to 1 024 per pass.  ``'bounds'`` pins
+      every eccentricity from well-chosen BFS sources by the triangle-inequality bounds of Takes and Kosters (2013) --
+      ecc(v) <= d(v, s) + ecc(s) and ecc(v) >= max(d(v, s), ecc(s) - d(v, s)) -- up to 64 `words` sources per round, two
+      BFS passes per round, until the bounds meet everywhere; networkx's ``_extrema_bounding`` does the same one source
+      at a time.  Both are exact.  The bounds need d(s, v) = d(v, s): a directed graph, a single node and an nbunch
+      silently take ``'all'``.  ``'bounds'`` is not the default because it lost where it was measured: on the 1 M-node
+      BA graph (m = 10; eccentricities 4 to 6) the bounds of most nodes never meet, 48 % of the nodes become sources
+      and it takes 4.3 s against 2.45 s (``profiles/eccentricity.txt``); graphs of large diameter prune better.  Worst
+      case: a vertex-transitive graph such as a cycle never prunes, every node becomes a source, and the cost is
+      twice that of ``'all'``
+    :param weight: must be None (weighted distances need a shortest-path search by weight, not implemented here);
+      networkx's ``sp`` is not offered
+    :param words: 64-bit source words per BFS pass (1, 2, 4, 8 or 16; 0 = the library's choice, for ``'bounds'`` 16)
+    :return: int64 Series named ``eccentricity`` indexed by the sorted node labels (the index of ``node_measures``) or
+      by the sorted members of `v`; an int for a single node; equal to networkx
+    :raises networkx.NetworkXError: G is not connected / not strongly connected (networkx's two messages); `v` is
+      neither a node nor a sequence of nodes
+    :raises NotImplementedError: weight is not None; G is directed and its adapter has no in-adjacency
+    :raises ValueError: an unknown method
+    """
+    _distance_arguments('eccentricity', weight, 'weight')
+    if method not in ('bounds', 'all'):
+        raise ValueError(f"method must be 'bounds' or 'all', got {method!r}")
+    graph = _adapter(G)
+    single = False
+    if v is not None:
+        try:
+            single = v in set(graph.get_nodes())
+        except TypeError:                                      # unhashable: a container of nodes
+            pass
+    targets = _node_set(graph, v)
+    if not targets:                                             # the empty graph, or no member in `v`: networkx's {}
+        return pd.Series([], index=pd.Index([]), dtype=np.int64, name='eccentricity')
+    K = graph._K()
+    host = graph._device_graph()[0]
+    if v is None:
+        col, info = _eccentricity_column(graph, K, method, words)
+        series = graph._frame(['eccentricity'], [col], [np.dtype('int64')])['eccentricity']
+        series.attrs.update(info)
+        return series
+    rows = np.sort(_rows_of(graph, targets))                    # rows of the sorted labels
+    ecc = _eccentricity_of_rows(graph, K, np.asarray(host.inv)[rows], words)
+    values = np.asarray(K.to_host(ecc)).astype(np.int64)
+    if single:
+        return int(values[0])
+    return pd.Series(values, index=_label_index(graph)[rows], name='eccentricity')
+
+
+def _eccentricities(G, e):
+    """(labels, values) of the eccentricities `e` (a Series of ``eccentricity`` or networkx's dict), computed when
+    None; fails on an empty graph as networkx's max() / min() of no values does."""
+    if e is None:
+        e = eccentricity(G)
+    if isinstance(e, pd.Series):
+        labels, values = list(e.index), e.to_numpy()
+    else:
+        labels, values = list(e), np.asarray(list(e.values()))
+    if not len(labels):
+        raise ValueError('max() arg is an empty sequence: the graph has no node')
+    return labels, values
+
+
+def diameter(G, e=None, usebounds: bool = False) -> int:
+    """
+    ``nx.diameter(G, e)``: the largest eccentricity, from ``eccentricity(G)`` or the precomputed `e` (its Series, or a
+    dict as networkx takes).  `usebounds` is accepted and ignored: pass ``e=eccentricity(G, method='bounds')`` for the
+    bounds method (networkx's flag selects a different early exit per function, which is not restated).
+
+    :raises networkx.NetworkXError: G is not (strongly) connected
+    :raises ValueError: G has no node (as networkx)
+    """
+    return int(_eccentricities(G, e)[1].max())
+
+
+def radius(G, e=None, usebounds: bool = False) -> int:
+    """``nx.radius(G, e)``: the smallest eccentricity; arguments and errors as ``diameter``."""
+    return int(_eccentricities(G, e)[1].min())
+
+
+def center(G, e=None, usebounds: bool = False) -> list:
+    """
+    ``nx.center(G, e)``: the nodes whose eccentricity equals the radius; arguments and errors as ``diameter``.
+
+    :return: list of node labels in index order (sorted labels; the order of `e` when it is given).  Stated
+      divergence: networkx lists the same nodes in the graph's own node order
+    """
+    labels, values = _eccentricities(G, e)
+    return [labels[i] for i in np.nonzero(values == values.min())[0]]
+
+
+def periphery(G, e=None, usebounds: bool = False) -> list:
+    """
+    ``nx.periphery(G, e)``: the nodes whose eccentricity equals the diameter; arguments and errors as ``diameter``.
+
+    :return: list of node labels in index order (sorted labels; the order of `e` when it is given).  Stated
+      divergence: networkx lists the same nodes in the graph's own node order
+    """
+    labels, values = _eccentricities(G, e)
+    return [labels[i] for i in np.nonzero(values == values.max())[0]]

@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures)
+#define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
+                                    grx_eccentricity joined later under the same number (an added entry point only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -878,6 +879,33 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
                       int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
                       int64_t *d_reach, int64_t *d_dsum, double *d_harmonic, void *d_workspace,
                       size_t workspace_bytes, void *stream);
+
+/*
+ * grx_eccentricity: the eccentricity of many BFS sources at once, and bounds on the eccentricity of every node -- what
+ *   networkx.eccentricity(G, v) (distance_measures.py) computes one BFS per node.  The graph, the source list, `words`
+ *   and the pulling direction are those of grx_distance_sums (same bitset BFS, S = 64 words sources per batch; state
+ *   24 n words bytes).  Per batch, pass A runs one BFS:
+ *     source_ecc[b] = the largest d(s_b, v) over the nodes v that s_b reaches; 0 when it reaches nothing (or when
+ *                     s_b lies outside [0, n): such an id is never written through)
+ *     reach[v]     += number of the batch's sources s != v with a path s -> v (a repeated id counts per occurrence)
+ *     lower[v]      = max(lower[v], largest d(s, v) over those sources): the per-target maximum distance
+ *   With d_upper non-NULL pass B replays the batch's BFS, source_ecc now known, and tightens the eccentricity bounds of
+ *   Takes and Kosters ("Computing the eccentricity distribution of large graphs", 2013) for every v and every source s
+ *   of the batch with a path to v at distance d >= 0 (d = 0: v = s):
+ *     upper[v] = min(upper[v], d + source_ecc[s]),   lower[v] = max(lower[v], source_ecc[s] - d)
+ *   so that lower[s] = upper[s] = source_ecc[s] at every source.  Pass B is VALID ONLY ON A SYMMETRIC CSR (an undirected
+ *   graph, d(s, v) = d(v, s)) whose sources reach every node; then lower <= ecc <= upper elementwise.  On a directed
+ *   graph pass NULL for d_upper: source_ecc is right for any CSR, lower is then the per-target maximum only.
+ *   accumulate = 0: the call first sets reach = 0, lower = 0 and upper = INT32_MAX; 1: it continues from the caller's
+ *   arrays (bounds carried across calls).  d_source_ecc: int32[n_sources], overwritten; d_reach: int64[n]; d_lower,
+ *   d_upper: int32[n].  Integer arithmetic only; every output is the same for every `words`, source order and run.
+ *   n < 2^31.  d_workspace: grx_eccentricity_workspace_bytes(n, words, n_sources) bytes.
+ */
+size_t grx_eccentricity_workspace_bytes(int64_t n, int words, int64_t n_sources);
+int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                     int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
+                     int32_t *d_source_ecc, int64_t *d_reach, int32_t *d_lower, int32_t *d_upper, int accumulate,
+                     void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
  * grx_biconnected: for every node of an undirected graph the number of biconnected components it belongs to -- what
