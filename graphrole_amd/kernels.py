@@ -17,6 +17,9 @@ from . import _lib
 
 c_void_p = ctypes.c_void_p
 HUB_FACTOR = 32          # GRX_HUB_FACTOR in csrc/grx_common.h
+SH_BLOCK = 256           # csrc/grx_structural_holes.hip: threads per workgroup,
+SH_ROW_MAX_WG = 2048     # workgroups of its row kernels (256 / lanes rows per workgroup pass)
+SH_ARC_MAX_WG = 8192     # and of its per-arc kernel (256 / lanes arcs per workgroup pass)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1327,3 +1330,36 @@ def core_numbers(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR] = None,
     _lib.call('grx_core_numbers', n, *_csr_args(csr_out), *_csr_args(csr_in), _ptr(core), _ptr(onion),
               ctypes.byref(n_rounds), _ptr(ws), ws_bytes, _stream())
     return core, onion, int(n_rounds.value)
+
+
+def _hubs_for(csr: DeviceCSR, lanes: Optional[int]) -> tuple:
+    """(hub_rows, n_hubs, lanes_per_row) as C arguments: the CSR's own, or -- for another lane width -- the rows longer
+    than 32 * lanes, which the kernels leave to their hub launch."""
+    if lanes is None or int(lanes) == csr.lanes_per_row:
+        return _ptr(csr.hub_rows), csr.n_hubs, csr.lanes_per_row, csr.hub_rows
+    rows = np.nonzero(np.diff(csr._host[0]) > HUB_FACTOR * int(lanes))[0].astype(np.int32)
+    hub_rows = torch.from_numpy(rows).to(device()) if len(rows) else None
+    return _ptr(hub_rows), int(len(rows)), int(lanes), hub_rows
+
+
+def structural_holes(csr: DeviceCSR, z: Optional[torch.Tensor] = None, out_row_ptr: Optional[torch.Tensor] = None,
+                     want_constraint: bool = True, want_effective_size: bool = False, want_local: bool = False,
+                     lanes: Optional[int] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor],
+                                                           Optional[torch.Tensor]]:
+    """grx_structural_holes on a structurally symmetric CSR: (constraint fp64[n], effective_size fp64[n] -- the
+    weighted-form sum --, local constraint fp64[nnz] per arc), None for an output that was not asked for.  z: fp64[nnz]
+    device tensor of the symmetric mutual weights (None = every z is 1; csr.w is NOT read unless passed here).
+    out_row_ptr: int64[n+1] device tensor, the row pointers of the graph's own out-adjacency (None = the CSR's): rows
+    empty there get NaN.  lanes = lanes per row and per arc (4, 8, 16 or 32; None = csr.lanes_per_row), with the hub
+    list of that width."""
+    if not (want_constraint or want_effective_size or want_local):
+        raise ValueError('structural_holes: no output asked for')
+    n = csr.n
+    ws, ws_bytes = _workspace('grx_structural_holes_workspace_bytes', n, csr.nnz)
+    con = torch.empty(max(n, 1), dtype=torch.float64, device=device()) if want_constraint else None
+    es = torch.empty(max(n, 1), dtype=torch.float64, device=device()) if want_effective_size else None
+    loc = torch.empty(max(csr.nnz, 1), dtype=torch.float64, device=device()) if want_local else None
+    hub_ptr, n_hubs, lanes_per_row, _keep = _hubs_for(csr, lanes)
+    _lib.call('grx_structural_holes', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(z), hub_ptr, n_hubs, lanes_per_row,
+              _ptr(out_row_ptr), _ptr(con), _ptr(es), _ptr(loc), _ptr(ws), ws_bytes, _stream())
+    return con, es, loc

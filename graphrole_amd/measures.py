@@ -10,7 +10,10 @@ the bitset multi-source BFS of csrc/grx_closeness.hip, the number of biconnected
 more than one: an articulation point) by the Tarjan-Vishkin sweeps of csrc/grx_biconnected.hip, and the core number
 and onion layer of every node (opt-in) by the synchronous peeling of csrc/grx_kcore.hip, and the eccentricity of every
 node (opt-in) -- with it diameter, radius, center and periphery -- by the extremal passes of the same multi-source
-BFS (grx_eccentricity in csrc/grx_closeness.hip).
+BFS (grx_eccentricity in csrc/grx_closeness.hip), and Burt's constraint of every node (opt-in) -- with it the weighted
+and directed form of effective size -- by the per-arc row intersections of csrc/grx_structural_holes.hip over the
+mutual-weight CSR, the first measures here besides ``weighted_degree``, ``pagerank`` and ``eigenvector`` that read an
+edge weight.
 """
 from __future__ import annotations
 
@@ -31,6 +34,7 @@ CATALOGUE = {
     'out_degree': 'G.out_degree()',
     'clustering': 'nx.clustering(G)',
     'effective_size': 'nx.effective_size(G)',
+    'constraint': 'nx.constraint(G, weight=weight)',
     'pagerank': "nx.pagerank(G, alpha, weight='weight', tol=tol, max_iter=max_iter)",
     'eigenvector': "nx.eigenvector_centrality(G, max_iter=max_iter, tol=tol, weight='weight')",
     'betweenness_centrality': 'nx.betweenness_centrality(G, k=k, normalized=normalized, endpoints=endpoints, '
@@ -44,11 +48,11 @@ CATALOGUE = {
 }
 
 #: catalogue entries computed only when named: not in ``available_measures`` nor in the default table -- the
-#: centralities and 'eccentricity' because they cost up to O(n m), 'biconnected_components', 'core_number' and
-#: 'onion_layer' (O(n + m)) because the default table and ``available_measures`` are pinned as they were before they
-#: existed
+#: centralities and 'eccentricity' because they cost up to O(n m), 'biconnected_components', 'core_number',
+#: 'onion_layer' (O(n + m)) and 'constraint' (a row intersection per arc) because the default table and
+#: ``available_measures`` are pinned as they were before they existed
 OPT_IN = ('betweenness_centrality', 'closeness_centrality', 'harmonic_centrality', 'biconnected_components',
-          'core_number', 'onion_layer', 'eccentricity')
+          'core_number', 'onion_layer', 'eccentricity', 'constraint')
 
 
 def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
@@ -62,6 +66,9 @@ def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
         if directed or multi:
             return (f'{name} of a {kind} is not computed here (only undirected graphs without parallel edges); '
                     f'use {CATALOGUE[name]} from networkx')
+    if name == 'constraint' and multi:
+        return (f'{name} of a {kind} is not computed here (networkx adds key dictionaries there, not weights: its '
+                f'result on a multigraph is not meaningful); merge the parallel edges first')
     if name == 'eigenvector' and multi:
         return f'networkx does not implement {CATALOGUE[name]} for a multigraph'
     if name == 'biconnected_components' and directed:
@@ -104,7 +111,7 @@ def _count_csrs(graph, K, host):
 
 def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                   max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                  endpoints: bool = False, wf_improved: bool = True) -> pd.DataFrame:
+                  endpoints: bool = False, wf_improved: bool = True, weight=None) -> pd.DataFrame:
     """
     Node x measure table of well-known graph measures, computed on the GPU.
 
@@ -117,13 +124,16 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       ``betweenness_centrality``); they apply to ``'betweenness_centrality'`` only
     :param wf_improved: networkx's argument of closeness_centrality; it applies to ``'closeness_centrality'`` only.
       ``'closeness_centrality'`` and ``'harmonic_centrality'`` named together share one multi-source BFS pass
+    :param weight: networkx's argument of constraint: None or ``'weight'`` (see ``constraint``); it applies to
+      ``'constraint'`` only
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
     :raises ValueError: an unknown measure name
     :raises NotImplementedError: a measure that networkx does not implement for this kind of graph (among them
       ``'biconnected_components'`` and ``'onion_layer'`` of a directed graph, and ``'core_number'`` and
       ``'onion_layer'`` of a multigraph or of a graph with a self-loop), or that is outside this implementation's scope
-      (directed / multigraph clustering and effective size)
+      (directed / multigraph clustering and effective size -- ``effective_size(G)`` computes the directed and the
+      weighted form --, ``'constraint'`` of a multigraph)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
     :raises networkx.NetworkXError: ``'eccentricity'`` of a graph that is not (strongly) connected, as networkx
 
@@ -131,12 +141,12 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     ZeroDivisionError).
     """
     return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter, k=k, seed=seed,
-                       normalized=normalized, endpoints=endpoints, wf_improved=wf_improved)
+                       normalized=normalized, endpoints=endpoints, wf_improved=wf_improved, weight=weight)
 
 
 def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                 max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                endpoints: bool = False, wf_improved: bool = True) -> pd.DataFrame:
+                endpoints: bool = False, wf_improved: bool = True, weight=None) -> pd.DataFrame:
     """``node_measures`` on an existing graph adapter (its device CSR is built once and reused)."""
     directed = bool(graph.directed)
     multi = bool(getattr(graph, '_multi', False))
@@ -156,6 +166,9 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
     peeled = [nm for nm in names if nm in ('core_number', 'onion_layer')]
     if peeled:
         _peeling_refusals(graph, peeled[0])                   # likewise: read from the host CSR
+    if 'constraint' in names:
+        weighted = _weight_flag('constraint', weight)
+        _structural_hole_refusals(graph, 'constraint', weighted)
     K = graph._K()
     host, out, tr = graph._device_graph()
     loops = bool(graph._has_loops)
@@ -211,6 +224,10 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col, dt = local()[0], np.dtype('float64')
         elif nm == 'effective_size':
             col, dt = local()[1], np.dtype('float64')
+        elif nm == 'constraint':
+            if 'constraint' not in cache:
+                cache['constraint'] = _structural_holes(graph, K, weighted, True, False)[0]
+            col, dt = cache['constraint'], np.dtype('float64')
         elif nm == 'betweenness_centrality':
             # BFS walks G[v]: the distinct arcs, out and (directed) in, not a neighbour multiset
             s_out, s_in = _structure_pair(graph, 'betweenness_centrality')
@@ -770,3 +787,159 @@ def periphery(G, e=None, usebounds: bool = False) -> list:
     """
     labels, values = _eccentricities(G, e)
     return [labels[i] for i in np.nonzero(values == values.max())[0]]
+
+
+# -------------------------------------------------------------------------------------------- structural holes
+def _weight_flag(name: str, weight) -> bool:
+    """networkx's `weight` argument of constraint / effective_size: None = every edge counts 1, 'weight' = the
+    attribute the adapters read (a CSRGraph's weight array; a missing attribute counts 1)."""
+    if weight is None:
+        return False
+    if isinstance(weight, str) and weight == 'weight':
+        return True
+    raise NotImplementedError(f"nx.{name}(G, weight={weight!r}): the graph adapters read the edge attribute 'weight' "
+                              f"only; pass weight=None or weight='weight', or use networkx")
+
+
+def _host_arcs(g):
+    """(src, dst, weights or None) of the host CSRGraph `g` as rows of the sorted labels: its edge arrays, or -- when it
+    carries an explicit neighbour order -- the arcs of its host CSR (an undirected edge then from both ends)."""
+    edges = g.edge_arrays()
+    if edges is not None:
+        return edges
+    rows = np.repeat(np.arange(g.n, dtype=np.int64), np.diff(g.row_ptr))
+    return rows, np.asarray(g.col, dtype=np.int64), g.w
+
+
+def _structural_hole_refusals(graph, name: str, weighted: bool) -> None:
+    """What constraint and the weighted effective size refuse, read from the host edge arrays: no device work."""
+    g = graph.to_csr()
+    multi = bool(getattr(graph, '_multi', False))
+    if not multi and hasattr(graph, '_is_simple') and not graph._is_simple():
+        multi = graph.get_num_edges() != g.num_edges
+    if multi:
+        raise NotImplementedError(_unavailable('constraint', bool(graph.directed), True))
+    if weighted:
+        w = _host_arcs(g)[2]
+        if w is not None and len(w) and (not np.all(np.isfinite(w)) or np.min(w) < 0):
+            raise ValueError(f'{name}: edge weights must be finite and >= 0 (networkx computes with whatever it is '
+                             f'given; a negative mutual weight has no meaning as a share of attention)')
+
+
+def _mutual_weight_csr(graph, K, weighted: bool):
+    """(device CSR, z, out_row_ptr) of grx_structural_holes: the structurally symmetric CSR of networkx's
+    all_neighbors in internal row order, its mutual weights z(u, v) = w(u -> v) + w(v -> u) (None = all 1) and the row
+    pointers that tell len(G[u]) (None = the CSR's own).  Cached on the adapter per `weighted`."""
+    cache = graph.__dict__.setdefault('_mutual_weight', {})
+    if weighted in cache:
+        return cache[weighted]
+    host, out, _ = graph._device_graph()
+    if not graph.directed:
+        # networkx's mutual weight of an undirected edge is 2 w (a self-loop: 2 w(u, u) as well).  The factor 2 is a
+        # power of two and cancels exactly in P = z / sum z and M = z / max z, so the out CSR's own weights serve as z
+        cache[weighted] = (out, out.w if weighted else None, None)
+        return cache[weighted]
+    # directed: the union of the arcs and their reverses in internal row order, the weights of an arc and of its
+    # reverse summed -- a reciprocal pair gets w(u -> v) + w(v -> u) from both ends, a loop counts twice
+    g = graph.to_csr()
+    src, dst, w = _host_arcs(g)
+    n = g.n
+    inv = np.asarray(host.inv, dtype=np.int64)
+    a, b = inv[np.asarray(src, dtype=np.int64)], inv[np.asarray(dst, dtype=np.int64)]
+    vals = np.ones(len(a)) if (w is None or not weighted) else np.asarray(w, dtype=np.float64)
+    key, inverse = np.unique(np.concatenate([a, b]) * np.int64(max(n, 1)) + np.concatenate([b, a]),
+                             return_inverse=True)
+    z = np.bincount(inverse, weights=np.concatenate([vals, vals]), minlength=len(key))
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=row_ptr[1:])
+    csr = K.DeviceCSR(row_ptr, (key % max(n, 1)).astype(np.int32), z)
+    cache[weighted] = (csr, csr.w, out.row_ptr)
+    return cache[weighted]
+
+
+def _structural_holes(graph, K, weighted: bool, want_constraint: bool, want_effective_size: bool):
+    """(constraint, effective size) device columns in internal row order, None for the one not asked for."""
+    csr, z, out_row_ptr = _mutual_weight_csr(graph, K, weighted)
+    con, es, _ = K.structural_holes(csr, z, out_row_ptr, want_constraint=want_constraint,
+                                    want_effective_size=want_effective_size)
+    return con, es
+
+
+def _member_rows(graph, nodes) -> Optional[np.ndarray]:
+    """Rows of the sorted labels of the members of `nodes`, ascending and distinct; None for nodes=None.  A member that
+    is not a node raises KeyError, as networkx's ``G[v]``."""
+    if nodes is None:
+        return None
+    nodes = list(nodes)
+    members = set(graph.get_nodes())
+    for v in nodes:
+        if v not in members:
+            raise KeyError(v)
+    return np.unique(_rows_of(graph, nodes))
+
+
+def _structural_hole_series(G, name: str, nodes, weight) -> pd.Series:
+    weighted = _weight_flag(name, weight)
+    graph = _adapter(G)
+    _structural_hole_refusals(graph, name, weighted)
+    rows = _member_rows(graph, nodes)
+    if name == 'effective_size' and not graph.directed and not weighted:
+        # networkx's ego-graph formula n - 2t/n: the existing column, unchanged
+        series = measures_of(graph, ['effective_size'])['effective_size']
+    elif graph.to_csr().n == 0:
+        series = pd.Series([], index=pd.Index([]), dtype=np.float64, name=name)
+    else:
+        K = graph._K()
+        con, es = _structural_holes(graph, K, weighted, name == 'constraint', name == 'effective_size')
+        series = graph._frame([name], [con if name == 'constraint' else es], [np.dtype('float64')])[name]
+    return series if rows is None else series.iloc[rows]
+
+
+def constraint(G, nodes=None, weight=None) -> pd.Series:
+    """
+    Burt's constraint of every node on the GPU -- how much of a node's attention goes to contacts that are themselves
+    tied to one another; a low value marks a broker across structural holes: ``nx.constraint(G, nodes, weight)`` of
+    networkx 3.4.2 (structuralholes.py) by grx_structural_holes (csrc/grx_structural_holes.hip), a row intersection
+    per arc of the mutual-weight CSR.  With z(u, v) = w(u -> v) + w(v -> u), P(u, v) = z(u, v) / sum_x z(u, x):
+    constraint(u) = sum_v (P(u, v) + sum_w P(u, w) P(w, v))^2 over the neighbours v, w of u in either direction.
+
+    :param G: any graph ``node_measures`` accepts, undirected or directed, with or without self-loops
+    :param nodes: None = every node; otherwise an iterable of nodes
+    :param weight: None = every edge counts 1; ``'weight'`` = the edge attribute the adapters read (a ``CSRGraph``'s
+      weight array; a missing attribute counts 1)
+    :return: float64 Series named ``constraint`` indexed by the sorted node labels (the index of ``node_measures``) or
+      by the sorted members of `nodes`; NaN for a node without an out-neighbour (networkx: ``len(G[v]) == 0``, in a
+      directed graph even when the node has in-arcs)
+    :raises NotImplementedError: another `weight` (a different attribute name, a callable); a multigraph or parallel
+      edges
+    :raises ValueError: a negative or non-finite weight
+    :raises KeyError: a member of `nodes` is not a node (as networkx)
+
+    Stated divergences: `weight` is None or ``'weight'``; a multigraph raises (networkx adds the key dictionaries of
+    the parallel edges, which is not meaningful); negative and non-finite weights raise (networkx computes with them);
+    ``nx.local_constraint(G, u, v)`` is not offered (pairs that are not adjacent need another access pattern; the
+    kernel returns it per arc).  Values agree with networkx to 1e-12 relative, not bit for bit: every quotient and
+    product is networkx's own IEEE operation, but the sums -- sum_x z(u, x) among them, whose order networkx takes from
+    a set -- are added in another order.
+    """
+    return _structural_hole_series(G, 'constraint', nodes, weight)
+
+
+def effective_size(G, nodes=None, weight=None) -> pd.Series:
+    """
+    Burt's effective size of every node's ego network on the GPU: ``nx.effective_size(G, nodes, weight)`` of networkx
+    3.4.2 (structuralholes.py).  For an undirected graph with ``weight=None`` it is networkx's ego-graph formula
+    n - 2t/n, the ``'effective_size'`` column of ``node_measures`` unchanged; with a `weight` or for a directed graph
+    it is sum_v (1 - sum_w P(u, w) M(v, w)), M(v, w) = z(v, w) / max_x z(v, x), from the same kernel call as
+    ``constraint`` (grx_structural_holes).
+
+    :param G, nodes, weight: as ``constraint``
+    :return: float64 Series named ``effective_size``, indexed as ``constraint``'s; NaN for a node without an
+      out-neighbour
+    :raises NotImplementedError, ValueError, KeyError: as ``constraint``
+
+    Stated divergences: those of ``constraint``; the weighted form agrees with networkx to 1e-12 times the number of
+    neighbours, absolute (its terms cancel).  ``node_measures(D, ['effective_size'])`` of a directed graph still
+    raises: this function is the way in.
+    """
+    return _structural_hole_series(G, 'effective_size', nodes, weight)

@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
-                                    grx_eccentricity joined later under the same number (an added entry point only)
+                                    grx_eccentricity and grx_structural_holes joined later under the same number (added
+                                    entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -964,6 +965,41 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
                      int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
                      const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, int64_t *d_core,
                      int64_t *d_onion, int64_t *n_rounds, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_structural_holes: Burt's structural-hole measures of every node -- networkx.constraint(G, weight=...),
+ *   networkx.local_constraint of every arc and the weighted / directed form of networkx.effective_size
+ *   (networkx/algorithms/structuralholes.py).  With z(u, v) networkx's mutual_weight w(u -> v) + w(v -> u),
+ *     S(u) = sum_x z(u, x),  X(u) = max_x z(u, x),  P(u, v) = z(u, v) / S(u),  M(v, w) = z(v, w) / X(v)   (0 / 0 = 0)
+ *     local(u, v)       = (P(u, v) + sum_w P(u, w) P(w, v))^2        constraint(u) = sum_v local(u, v)
+ *     effective_size(u) = sum_v (1 - sum_w P(u, w) M(v, w))
+ *   v over the entries of row u (u itself when it has a self-loop), w over the common entries of rows u and v.
+ *   d_row_ptr / d_col: a CSR that is SYMMETRIC in structure (entry (u, v) iff entry (v, u)); columns ascending and
+ *   distinct inside a row; a diagonal entry is allowed.  Rows in any order.  Rows longer than GRX_HUB_FACTOR *
+ *   lanes_per_row (4, 8, 16 or 32) must be listed in d_hub_rows.
+ *   d_z: fp64[nnz], the mutual weights: symmetric (the value at arc (u, v) equals the value at (v, u)), finite and
+ *   >= 0; NULL = every z is 1 (P and M then come from the row lengths alone).  A common factor of all z cancels in P
+ *   and M: an undirected graph may pass its edge weights w for z = 2 w.
+ *   d_out_row_ptr: int64[n+1], the row pointers of the graph's own out-adjacency in the same row order, or NULL = those
+ *   of the CSR itself.  A node whose row is empty THERE gets NaN in both node outputs (networkx: len(G[v]) == 0; a
+ *   directed node with in-arcs only).  Only the row lengths are read.
+ *   d_constraint, d_effective_size: fp64[n] or NULL.  d_local: fp64[nnz] or NULL, local(u, v) at arc (u, v).  At least
+ *   one must be given.  d_effective_size always holds the sum above; for an undirected graph without weights networkx
+ *   uses the ego-graph formula n - 2t/n instead (grx_local_structure_measures), which is the caller's choice.
+ *   Method: see the header of csrc/grx_structural_holes.hip: row statistics, then one lane group per ARC that walks
+ *   the shorter of the two rows and binary-searches the longer one, then a per-row sum of the arc terms.  Bound: the
+ *   sum over arcs of min(d_u, d_v) * ceil(log2 max(d_u, d_v)) dependent 4-byte gathers plus two 8-byte gathers per
+ *   common neighbour.  Every quotient and product is its own IEEE operation; sums are lane-strided with a fixed
+ *   butterfly.  No floating-point atomics: every output has the same bits in every run.
+ *   n < 2^31.  d_workspace: grx_structural_holes_workspace_bytes(n, nnz) bytes (16 n + 20 nnz), nnz = row_ptr[n]; the
+ *   call reads row_ptr[n] back to check it and so waits for the stream once, before its first launch.
+ */
+size_t grx_structural_holes_workspace_bytes(int64_t n, int64_t nnz);
+int grx_structural_holes(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_z,
+                         const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                         const int64_t *d_out_row_ptr,
+                         double *d_constraint, double *d_effective_size, double *d_local,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
