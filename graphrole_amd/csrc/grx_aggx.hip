@@ -171,12 +171,6 @@ __global__ __launch_bounds__(256) void med_select_kernel(const int64_t *__restri
     }
 }
 
-int grid_for(int64_t items)
-{
-    const int64_t want = grx_ceil_div(items, 256);
-    return (int)(want < 1 ? 1 : (want > GRX_NUM_CU * 32 ? GRX_NUM_CU * 32 : want));
-}
-
 }  // namespace
 
 extern "C" {
@@ -185,7 +179,7 @@ int grx_convert_i64_to_f64(int64_t n, const int64_t *d_in, double *d_out, void *
 {
     if (n <= 0) return GRX_OK;
     GRX_REQUIRE(d_in && d_out, "grx_convert_i64_to_f64: NULL pointer");
-    convert_i64_f64_kernel<<<grid_for(n), 256, 0, grx_stream(stream)>>>(n, reinterpret_cast<const long long *>(d_in), d_out);
+    convert_i64_f64_kernel<<<grx_grid(n, 256, GRX_NUM_CU * 32), 256, 0, grx_stream(stream)>>>(n, reinterpret_cast<const long long *>(d_in), d_out);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }
@@ -194,7 +188,7 @@ int grx_convert_f64_to_i64(int64_t n, const double *d_in, int64_t *d_out, void *
 {
     if (n <= 0) return GRX_OK;
     GRX_REQUIRE(d_in && d_out, "grx_convert_f64_to_i64: NULL pointer");
-    convert_f64_i64_kernel<<<grid_for(n), 256, 0, grx_stream(stream)>>>(n, d_in, reinterpret_cast<long long *>(d_out));
+    convert_f64_i64_kernel<<<grx_grid(n, 256, GRX_NUM_CU * 32), 256, 0, grx_stream(stream)>>>(n, d_in, reinterpret_cast<long long *>(d_out));
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }
@@ -206,7 +200,7 @@ int grx_aggregate_i64(const int64_t *d_row_ptr, const int32_t *d_col, int f, con
     GRX_REQUIRE(f >= 0 && ldr >= f && row_begin >= 0 && row_begin <= row_end && ld >= row_end, "grx_aggregate_i64: bad shape");
     if (f == 0 || row_end == row_begin) return GRX_OK;
     GRX_REQUIRE(d_row_ptr && d_col && d_rows, "grx_aggregate_i64: NULL pointer");
-    aggregate_i64_kernel<<<grid_for((row_end - row_begin) * f), 256, 0, grx_stream(stream)>>>(
+    aggregate_i64_kernel<<<grx_grid((row_end - row_begin) * f, 256, GRX_NUM_CU * 32), 256, 0, grx_stream(stream)>>>(
         d_row_ptr, d_col, reinterpret_cast<const long long *>(d_rows), ldr, f, row_begin, row_end,
         reinterpret_cast<long long *>(d_sum), reinterpret_cast<long long *>(d_prod), reinterpret_cast<long long *>(d_min),
         reinterpret_cast<long long *>(d_max), ld);
@@ -220,7 +214,7 @@ int grx_aggregate_count(const int64_t *d_row_ptr, int f, int64_t row_begin, int6
     GRX_REQUIRE(f >= 0 && row_begin >= 0 && row_begin <= row_end && ld >= row_end, "grx_aggregate_count: bad shape");
     if (f == 0 || row_end == row_begin) return GRX_OK;
     GRX_REQUIRE(d_row_ptr && d_out, "grx_aggregate_count: NULL pointer");
-    count_kernel<<<grid_for(row_end - row_begin), 256, 0, grx_stream(stream)>>>(d_row_ptr, row_begin, row_end, f, as_i64, d_out, ld);
+    count_kernel<<<grx_grid(row_end - row_begin, 256, GRX_NUM_CU * 32), 256, 0, grx_stream(stream)>>>(d_row_ptr, row_begin, row_end, f, as_i64, d_out, ld);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }
@@ -244,11 +238,10 @@ int grx_aggregate_median(const int64_t *d_row_ptr, const int32_t *d_col, int f, 
     GRX_REQUIRE(workspace_bytes >= grx_aggregate_median_workspace_bytes(e_end - e_begin), "grx_aggregate_median: workspace too small");
     hipStream_t st = grx_stream(stream);
     uint64_t *vals = reinterpret_cast<uint64_t *>(d_workspace);
-    const int64_t want = grx_ceil_div(row_end - row_begin, 4);
-    const int sgrid = (int)(want > GRX_NUM_CU * 32 ? GRX_NUM_CU * 32 : (want < 1 ? 1 : want));
+    const unsigned sgrid = grx_grid(row_end - row_begin, 4, GRX_NUM_CU * 32);
     for (int c = 0; c < f; ++c) {
         if (e_end > e_begin)
-            med_gather_kernel<<<grid_for(e_end - e_begin), 256, 0, st>>>(d_col, d_rows, ldr, c, e_begin, e_end, vals);
+            med_gather_kernel<<<grx_grid(e_end - e_begin, 256, GRX_NUM_CU * 32), 256, 0, st>>>(d_col, d_rows, ldr, c, e_begin, e_end, vals);
         med_select_kernel<<<sgrid, 256, 0, st>>>(d_row_ptr, row_begin, row_end, e_begin, vals, d_median + (int64_t)c * ld);
         GRX_LAUNCH_CHECK();
     }

@@ -136,8 +136,25 @@ int grx_internal_sort_u64(int64_t n, const uint64_t *keys, uint64_t *out, void *
 int grx_internal_vertical_log_bin(int64_t n, int ncols, const double *d_cols, int64_t ld, const uint8_t *h_is_i64, double frac,
                                   uint8_t *d_bins, int64_t ld_bins, int32_t *d_nbins, void *d_workspace,
                                   size_t workspace_bytes, int32_t *d_status, void *stream);
-// grx_graph.hip
+// grx_aggregate.hip
 int64_t grx_internal_plan_max_degree(const grx_aggregate_plan *plan);
+
+// Streams that are read exactly once per launch (the neighbour index list, the oriented arc tables, the output
+// columns) can carry the non-temporal hint so that they do not evict the hot rows / hub lists the random gathers of
+// the same kernel hit in L2.  MEASURED WITHOUT GAIN on MI355X (round 3, -DGRX_NT_STREAMS=1 against 0: aggregation
+// 1.011 vs 0.995 ms per step at BA 1 M, 12.95 vs 12.33 ms at config 5, triangle counting 0.588 vs 0.585): the L2 hit
+// rate of these kernels is set by how many gather rows fit (sqrt(C / N) on a power-law graph), not by what the
+// streams displace.  Off by default; the macro stays for the next experiment.  (grx_gen0.hip, grx_aggregate.hip)
+#ifndef GRX_NT_STREAMS
+#define GRX_NT_STREAMS 0
+#endif
+#if GRX_NT_STREAMS
+#define GRX_STREAM_LD(p) __builtin_nontemporal_load(&(p))
+#define GRX_STREAM_ST(p, v) __builtin_nontemporal_store((v), &(p))
+#else
+#define GRX_STREAM_LD(p) (p)
+#define GRX_STREAM_ST(p, v) ((p) = (v))
+#endif
 
 // Fixed-shape butterfly: every lane ends with the same total, the addition tree depends only
 // on WIDTH, so results are bitwise reproducible.

@@ -245,7 +245,7 @@ def test_triangle_counts_long_oriented_lists(K):
 def test_triangle_counts_concentrated_on_hubs(K):
     """Every corner of every triangle is an atomic increment of T[vertex], and atomics to one address queue up: the
     counters of the first 256 vertices of the degree-descending order are collected per workgroup in LDS
-    (csrc/grx_graph.hip, triangle_count_arcs_kernel) and added once per workgroup.  Graphs that send almost every
+    (csrc/grx_gen0.hip, triangle_count_arcs_kernel) and added once per workgroup.  Graphs that send almost every
     increment to a handful of hubs, with counts known in closed form:
       * h hubs joined to each other and to every one of m leaves (no leaf-leaf edges): a leaf closes C(h, 2) triangles,
         a hub (h - 1) m + C(h - 1, 2) -- hub counters far beyond 2^16, leaves beyond index 256 untouched by LDS;

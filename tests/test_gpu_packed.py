@@ -118,6 +118,26 @@ def test_every_output_count_and_both_row_widths(n_out):
         assert torch.equal(K.aggregate_packed(dev, L, rows), K.aggregate(dev, fp, n_out, ldr))
 
 
+def test_packed_slot_widths_2_and_8():
+    """aggregate_packed_kernel is built for S = 2, 4 and 8 lanes per output row and the suite runs the default S = 4.
+    GRX_PACKED_SLOTS (tools/tune_packed.sh) is read once per process, so a fresh child per width runs the cases that
+    cover F = 1 .. 8, both row widths, every cnt % 8, a row beyond the 8192 chunk and empty rows -- S = 2 runs four accumulators
+    per lane through the one-trip loop, S = 8 a single accumulator through the two-trips-per-iteration loop."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for slots in ('2', '8'):
+        env = dict(os.environ, GRX_PACKED_SLOTS=slots)
+        res = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(root, 'tests', 'test_gpu_packed.py'), '-q', '-m', 'gpu', '-x',
+                              '-k', '(test_every_output_count_and_both_row_widths or '
+                                    'test_packed_equals_fp64_with_a_very_long_row_and_dangling_nodes) and not '
+                                    'test_packed_slot_widths_2_and_8', '-p', 'no:cacheprovider'],
+                             capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert res.returncode == 0, (slots, res.stdout[-3000:] + res.stderr[-2000:])
+        assert '6 passed' in res.stdout, (slots, res.stdout[-1000:])
+
+
 def test_layout_limits():
     from graphrole_amd import _lib, kernels as K
     assert K.packed_layout([20, 20, 20], 0, [0, 1, 2], [0, 0, 0])[1] == 8
