@@ -254,6 +254,10 @@ _SIGNATURES = {
     'grx_eccentricity_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
     'grx_eccentricity': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'grx_weighted_distances_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
+    'grx_weighted_distances': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                       c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
     'grx_biconnected_workspace_bytes': (c_size_t, [c_int64]),
     'grx_biconnected': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int64), c_void_p, c_size_t, c_void_p]),

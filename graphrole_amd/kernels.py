@@ -1299,6 +1299,27 @@ def eccentricity_pass(csr_pull: DeviceCSR, sources: np.ndarray, words: int = 0, 
     return source_ecc[:len(src)], reach, lower, upper
 
 
+def weighted_distances(csr_pull: DeviceCSR, sources: np.ndarray, batch: int = 0, want_matrix: bool = False):
+    """grx_weighted_distances: (reach int64[n], dsum fp64[n], harmonic fp64[n], far fp64[n], source_ecc
+    fp64[len(sources)], dist fp64[len(sources), n] or None, rounds) of the shortest paths by weight from `sources`
+    (internal row ids, summed in that order) pulled over csr_pull with its weights csr_pull.w (None: every arc counts
+    1), as ``distance_sums`` pulls.  batch = sources per batch (16, 32 or 64; 0 = the library's choice);
+    want_matrix: also the source-major distance matrix, inf where there is no path."""
+    n = csr_pull.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    ws, ws_bytes = _workspace('grx_weighted_distances_workspace_bytes', n, int(batch), len(src))
+    reach = torch.empty(max(n, 1), dtype=torch.int64, device=device())
+    dsum, harmonic, far = (torch.empty(max(n, 1), dtype=torch.float64, device=device()) for _ in range(3))
+    source_ecc = torch.empty(max(len(src), 1), dtype=torch.float64, device=device())
+    dist = torch.empty((len(src), n), dtype=torch.float64, device=device()) if want_matrix else None
+    rounds = ctypes.c_int64(0)
+    _lib.call('grx_weighted_distances', n, _ptr(csr_pull.row_ptr), _ptr(csr_pull.col), _ptr(csr_pull.w),
+              _ptr(csr_pull.hub_rows), csr_pull.n_hubs, csr_pull.lanes_per_row, _ptr(src), len(src), int(batch),
+              _ptr(reach), _ptr(dsum), _ptr(harmonic), _ptr(far), _ptr(source_ecc), _ptr(dist), n,
+              ctypes.byref(rounds), _ptr(ws), ws_bytes, _stream())
+    return reach, dsum, harmonic, far, source_ecc[:len(src)], dist, int(rounds.value)
+
+
 def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor],
                                                                     Optional[torch.Tensor], int]:
     """grx_biconnected on the symmetric CSR of an undirected graph's distinct arcs: (count int64[n] = the number of

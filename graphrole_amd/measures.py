@@ -13,10 +13,13 @@ node (opt-in) -- with it diameter, radius, center and periphery -- by the extrem
 BFS (grx_eccentricity in csrc/grx_closeness.hip), and Burt's constraint of every node (opt-in) -- with it the weighted
 and directed form of effective size -- by the per-arc row intersections of csrc/grx_structural_holes.hip over the
 mutual-weight CSR, the first measures here besides ``weighted_degree``, ``pagerank`` and ``eigenvector`` that read an
-edge weight.
+edge weight, and -- with ``node_measures(..., distance='weight')`` -- closeness, harmonic centrality and eccentricity
+over shortest paths by edge weight, together with the distances themselves (``dijkstra_path_lengths``), by the batched
+Bellman-Ford relaxation of csrc/grx_sssp.hip, whose fixed point is networkx's Dijkstra distance bit for bit.
 """
 from __future__ import annotations
 
+import copy
 import random
 from numbers import Integral
 from typing import List, Optional, Sequence
@@ -39,12 +42,12 @@ CATALOGUE = {
     'eigenvector': "nx.eigenvector_centrality(G, max_iter=max_iter, tol=tol, weight='weight')",
     'betweenness_centrality': 'nx.betweenness_centrality(G, k=k, normalized=normalized, endpoints=endpoints, '
                               'seed=seed)',
-    'closeness_centrality': 'nx.closeness_centrality(G, wf_improved=wf_improved)',
-    'harmonic_centrality': 'nx.harmonic_centrality(G)',
+    'closeness_centrality': 'nx.closeness_centrality(G, distance=distance, wf_improved=wf_improved)',
+    'harmonic_centrality': 'nx.harmonic_centrality(G, distance=distance)',
     'biconnected_components': 'Counter(v for c in nx.biconnected_components(G) for v in c)',
     'core_number': 'nx.core_number(G)',
     'onion_layer': 'nx.onion_layers(G)',
-    'eccentricity': 'nx.eccentricity(G)',
+    'eccentricity': 'nx.eccentricity(G)',                      # distance='weight': nx.eccentricity(G, weight='weight')
 }
 
 #: catalogue entries computed only when named: not in ``available_measures`` nor in the default table -- the
@@ -111,7 +114,8 @@ def _count_csrs(graph, K, host):
 
 def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                   max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                  endpoints: bool = False, wf_improved: bool = True, weight=None) -> pd.DataFrame:
+                  endpoints: bool = False, wf_improved: bool = True, weight=None,
+                  distance=None) -> pd.DataFrame:
     """
     Node x measure table of well-known graph measures, computed on the GPU.
 
@@ -126,14 +130,20 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       ``'closeness_centrality'`` and ``'harmonic_centrality'`` named together share one multi-source BFS pass
     :param weight: networkx's argument of constraint: None or ``'weight'`` (see ``constraint``); it applies to
       ``'constraint'`` only
+    :param distance: None = the distance columns count hops; ``'weight'`` = ``'closeness_centrality'``,
+      ``'harmonic_centrality'`` and ``'eccentricity'`` measure shortest paths by the edge attribute ``'weight'`` (a
+      missing attribute counts 1), as networkx's ``distance='weight'`` resp. ``weight='weight'``: all three come from
+      one pass of grx_weighted_distances with every node a source, and ``'eccentricity'`` is then a float64 column.
+      It applies to these three columns only
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
-    :raises ValueError: an unknown measure name
+    :raises ValueError: an unknown measure name; ``distance='weight'`` with a negative, NaN or infinite edge weight
     :raises NotImplementedError: a measure that networkx does not implement for this kind of graph (among them
       ``'biconnected_components'`` and ``'onion_layer'`` of a directed graph, and ``'core_number'`` and
       ``'onion_layer'`` of a multigraph or of a graph with a self-loop), or that is outside this implementation's scope
       (directed / multigraph clustering and effective size -- ``effective_size(G)`` computes the directed and the
-      weighted form --, ``'constraint'`` of a multigraph)
+      weighted form --, ``'constraint'`` of a multigraph, weighted distances of a multigraph or of a graph with
+      parallel edges, a `distance` other than None and ``'weight'``)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
     :raises networkx.NetworkXError: ``'eccentricity'`` of a graph that is not (strongly) connected, as networkx
 
@@ -141,12 +151,13 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     ZeroDivisionError).
     """
     return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter, k=k, seed=seed,
-                       normalized=normalized, endpoints=endpoints, wf_improved=wf_improved, weight=weight)
+                       normalized=normalized, endpoints=endpoints, wf_improved=wf_improved, weight=weight,
+                       distance=distance)
 
 
 def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                 max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                endpoints: bool = False, wf_improved: bool = True, weight=None) -> pd.DataFrame:
+                endpoints: bool = False, wf_improved: bool = True, weight=None, distance=None) -> pd.DataFrame:
     """``node_measures`` on an existing graph adapter (its device CSR is built once and reused)."""
     directed = bool(graph.directed)
     multi = bool(getattr(graph, '_multi', False))
@@ -169,6 +180,9 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
     if 'constraint' in names:
         weighted = _weight_flag('constraint', weight)
         _structural_hole_refusals(graph, 'constraint', weighted)
+    by_weight = _distance_flag(distance) and any(nm in _DISTANCE_COLUMNS for nm in names)
+    if by_weight:
+        _weighted_distance_refusals(graph, "node_measures(G, ..., distance='weight')")
     K = graph._K()
     host, out, tr = graph._device_graph()
     loops = bool(graph._has_loops)
@@ -194,6 +208,13 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
         if 'distances' not in cache:
             cache['distances'] = _distance_sums(graph, K, np.arange(host.n, dtype=np.int64), reverse=False)
         return cache['distances']
+
+    def weighted_distances():
+        # every node a source, walking the out-arcs by weight: one pass for the three distance columns
+        if 'weighted_distances' not in cache:
+            cache['weighted_distances'] = K.weighted_distances(_weighted_pull(graph, 'weighted distances'),
+                                                               np.arange(host.n, dtype=np.int64))
+        return cache['weighted_distances']
 
     def blocks():
         # the undirected graph's distinct arcs: parallel edges count once
@@ -234,6 +255,17 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col = K.betweenness(s_out, s_in if directed else None, np.asarray(host.inv)[sources], endpoints,
                                 _rescale_factor(host.n, normalized, directed, k, endpoints))
             dt = np.dtype('float64')
+        elif nm == 'closeness_centrality' and by_weight:
+            reach, dsum = weighted_distances()[:2]
+            col = K.to_device(_closeness_by_weight(K.to_host(reach)[:host.n], K.to_host(dsum)[:host.n], host.n,
+                                                   wf_improved))
+            dt = np.dtype('float64')
+        elif nm == 'harmonic_centrality' and by_weight:
+            col, dt = weighted_distances()[2], np.dtype('float64')
+        elif nm == 'eccentricity' and by_weight:
+            reach, source_ecc = weighted_distances()[0], weighted_distances()[4]
+            _require_full_reach(K, reach, np.arange(host.n, dtype=np.int64), host.n, directed)
+            col, dt = source_ecc, np.dtype('float64')           # source b is row b: nothing to scatter
         elif nm == 'closeness_centrality':
             reach, dsum, _ = distances()
             col = K.to_device(_closeness(K.to_host(reach)[:host.n], K.to_host(dsum)[:host.n], host.n, wf_improved))
@@ -372,10 +404,130 @@ def _closeness(reach: np.ndarray, dsum: np.ndarray, n: int, wf_improved: bool) -
     return c
 
 
+def _closeness_by_weight(reach: np.ndarray, dsum: np.ndarray, n: int, wf_improved: bool) -> np.ndarray:
+    """``_closeness`` with totsp a sum of fp64 path lengths (networkx's ``distance=``): the same three IEEE operations,
+    dsum kept as it is."""
+    r = np.asarray(reach, dtype=np.int64).astype(np.float64)
+    t = np.asarray(dsum, dtype=np.float64)
+    ok = (t > 0) & (n > 1)
+    c = np.zeros(len(r))
+    c[ok] = r[ok] / t[ok]
+    if wf_improved and n > 1:
+        c[ok] *= r[ok] / float(n - 1)
+    return c
+
+
 def _distance_arguments(name: str, distance, keyword: str = 'distance') -> None:
     if distance is not None:
         raise NotImplementedError(f'weighted distances (nx.{name}(G, {keyword}={distance!r})) need a shortest-path '
-                                  f'search by weight and are not implemented here; use networkx')
+                                  f"search by weight, which this function does not run; "
+                                  f"node_measures(G, ['{name}'], distance='weight') computes the column by weight")
+
+
+#: the columns of ``node_measures`` that `distance` applies to
+_DISTANCE_COLUMNS = ('closeness_centrality', 'harmonic_centrality', 'eccentricity')
+
+
+def _distance_flag(distance) -> bool:
+    """networkx's `distance` argument of closeness / harmonic centrality (eccentricity: `weight`): None = hops,
+    'weight' = the attribute the adapters read (a CSRGraph's weight array; a missing attribute counts 1)."""
+    if distance is None:
+        return False
+    if isinstance(distance, str) and distance == 'weight':
+        return True
+    raise NotImplementedError(f"distance={distance!r}: the graph adapters read the edge attribute 'weight' only; pass "
+                              f"distance=None or distance='weight', or use networkx")
+
+
+def _has_parallel_edges(graph) -> bool:
+    """A multigraph, or an adapter whose graph holds parallel edges that ``to_csr()`` merged into one arc."""
+    if bool(getattr(graph, '_multi', False)):
+        return True
+    if hasattr(graph, '_is_simple') and not graph._is_simple():
+        return graph.get_num_edges() != graph.to_csr().num_edges
+    return False
+
+
+def _weighted_distance_refusals(graph, what: str) -> None:
+    """What the distances by weight refuse, read from the host edge arrays: no device work."""
+    if _has_parallel_edges(graph):
+        raise NotImplementedError(f'{what}: shortest paths by weight are not computed on a multigraph or a graph with '
+                                  f'parallel edges (their weights are summed into one arc here, where Dijkstra takes '
+                                  f'the lightest); merge the parallel edges first')
+    w = _host_arcs(graph.to_csr())[2]
+    if w is not None and len(w) and (not np.all(np.isfinite(w)) or np.min(w) < 0):
+        raise ValueError(f'{what}: edge weights must be finite and >= 0 (a shortest path by weight is not defined '
+                         f'otherwise; networkx raises or loops on such weights)')
+
+
+def _weighted_pull(graph, what: str):
+    """The weighted device CSR a walk along the out-arcs pulls over: the in-adjacency of a directed graph."""
+    _, out, tr = graph._device_graph()
+    if not graph.directed:
+        return out
+    if tr is None:
+        raise NotImplementedError(f'{type(graph).__name__} has no in-adjacency for this directed graph; '
+                                  f'{what} cannot be computed on it')
+    return tr
+
+
+#: largest distance matrix ``dijkstra_path_lengths`` returns
+_PATH_LENGTHS_MAX_BYTES = 2 << 30
+
+
+def dijkstra_path_lengths(G, sources=None, weight='weight') -> pd.DataFrame:
+    """
+    Shortest-path distances by edge weight on the GPU: row s is networkx 3.4.2's
+    ``single_source_dijkstra_path_length(G, s, weight=weight)``, bit for bit, by grx_weighted_distances
+    (csrc/grx_sssp.hip) -- a Bellman-Ford relaxation, up to 64 sources per batch, whose fixed point is the minimum over
+    the paths of the left-to-right fp64 sum of the weights: what Dijkstra returns when no weight is negative.
+
+    :param G: any graph ``node_measures`` accepts, without parallel edges.  A networkx multigraph and an igraph graph
+      with parallel edges are refused; a ``CSRGraph`` refuses duplicate edges when it is built, unless it was built with
+      ``validate=False`` -- then duplicates go unnoticed and their weights are summed into one arc
+    :param sources: node labels, one row each in the given order (a repeated label repeats its row); None = every node
+      in sorted order
+    :param weight: ``'weight'`` (a missing attribute counts 1) or None (every edge counts 1: hop counts)
+    :return: float64 DataFrame, rows = `sources`, columns = the sorted node labels, ``inf`` where there is no path (the
+      nodes networkx leaves out of its dict); ``.attrs['rounds']`` holds the relaxation rounds run
+    :raises ValueError: a negative, NaN or infinite weight; a result above 2 GiB (8 bytes x sources x nodes: ask for
+      fewer sources per call)
+    :raises NotImplementedError: a multigraph or parallel edges; another `weight`
+    :raises networkx.NodeNotFound: a source that is not a node
+    """
+    weighted = _weight_flag('single_source_dijkstra_path_length', weight)
+    graph = _adapter(G)
+    if weighted:
+        _weighted_distance_refusals(graph, 'dijkstra_path_lengths')
+    columns = _label_index(graph) if graph.to_csr().n else pd.Index([])
+    if sources is None:
+        labels = list(columns)
+    else:
+        labels = list(sources)
+        members = set(graph.get_nodes())
+        for v in labels:
+            if v not in members:
+                import networkx as nx
+                raise nx.NodeNotFound(f'Node {v} not found in graph')
+    n = len(columns)
+    if 8 * len(labels) * n > _PATH_LENGTHS_MAX_BYTES:
+        raise ValueError(f'dijkstra_path_lengths: {len(labels)} sources x {n} nodes is {8 * len(labels) * n} bytes of '
+                         f'distances, above the limit of 2 GiB ({_PATH_LENGTHS_MAX_BYTES} bytes); pass fewer sources '
+                         f'per call')
+    if not n or not labels:
+        return pd.DataFrame(np.empty((len(labels), n)), index=pd.Index(labels), columns=columns)
+    K = graph._K()
+    host = graph._device_graph()[0]
+    pull = _weighted_pull(graph, 'dijkstra_path_lengths')
+    if not weighted and pull.w is not None:
+        pull = copy.copy(pull)                                  # the same arrays, read without their weights
+        pull.w = None
+    rows = np.asarray(host.inv)[_rows_of(graph, labels)]
+    *_, dist, rounds = K.weighted_distances(pull, rows, want_matrix=True)
+    table = host.to_label_order(np.asarray(K.to_host(dist))[:len(labels), :n])
+    frame = pd.DataFrame(table, index=pd.Index(labels), columns=columns)
+    frame.attrs['rounds'] = rounds
+    return frame
 
 
 def _node_set(graph, nbunch) -> list:
@@ -410,7 +562,8 @@ def closeness_centrality(G, u=None, distance=None, wf_improved: bool = True):
     :param G: any graph ``node_measures`` accepts; multigraph edges count once, self-loops never shorten a path
     :param u: None = every node (every node is a BFS source; for a directed graph the distances d(v, u) run INTO u,
       as networkx's ``G.reverse()``); a node = that node only, one BFS along the reversed arcs
-    :param distance: must be None (weighted distances need a shortest-path search by weight, not implemented here)
+    :param distance: must be None here; ``node_measures(G, [...], distance='weight')`` computes the column over shortest
+      paths by weight
     :param wf_improved: as networkx: scale by the fraction of the other nodes that reach u
     :return: float64 Series indexed by the sorted node labels (the index of ``node_measures``), or a float for `u`
     :raises NotImplementedError: distance is not None
@@ -444,7 +597,8 @@ def harmonic_centrality(G, nbunch=None, distance=None, sources=None) -> pd.Serie
     :param G: any graph ``node_measures`` accepts; multigraph edges count once, self-loops never shorten a path
     :param nbunch: the nodes to return (networkx's ``G.nbunch_iter``: a node, an iterable whose non-members are
       dropped, or None = every node)
-    :param distance: must be None (weighted distances need a shortest-path search by weight, not implemented here)
+    :param distance: must be None here; ``node_measures(G, [...], distance='weight')`` computes the column over shortest
+      paths by weight
     :param sources: the BFS sources, likewise (duplicates count once)
     :return: float64 Series named ``harmonic_centrality`` indexed by the sorted members of `nbunch`
     :raises NotImplementedError: distance is not None
@@ -698,8 +852,8 @@ def eccentricity(G, v=None, method: str = 'all', weight=None, words: int = 0):
       and it takes 4.3 s against 2.45 s (``profiles/eccentricity.txt``); graphs of large diameter prune better.  Worst
       case: a vertex-transitive graph such as a cycle never prunes, every node becomes a source, and the cost is
       twice that of ``'all'``
-    :param weight: must be None (weighted distances need a shortest-path search by weight, not implemented here);
-      networkx's ``sp`` is not offered
+    :param weight: must be None here; ``node_measures(G, ['eccentricity'], distance='weight')`` computes the column
+      over shortest paths by weight.  networkx's ``sp`` is not offered
     :param words: 64-bit source words per BFS pass (1, 2, 4, 8 or 16; 0 = the library's choice, for ``'bounds'`` 16)
     :return: int64 Series named ``eccentricity`` indexed by the sorted node labels (the index of ``node_measures``) or
       by the sorted members of `v`; an int for a single node; equal to networkx
@@ -813,14 +967,10 @@ def _host_arcs(g):
 
 def _structural_hole_refusals(graph, name: str, weighted: bool) -> None:
     """What constraint and the weighted effective size refuse, read from the host edge arrays: no device work."""
-    g = graph.to_csr()
-    multi = bool(getattr(graph, '_multi', False))
-    if not multi and hasattr(graph, '_is_simple') and not graph._is_simple():
-        multi = graph.get_num_edges() != g.num_edges
-    if multi:
+    if _has_parallel_edges(graph):
         raise NotImplementedError(_unavailable('constraint', bool(graph.directed), True))
     if weighted:
-        w = _host_arcs(g)[2]
+        w = _host_arcs(graph.to_csr())[2]
         if w is not None and len(w) and (not np.all(np.isfinite(w)) or np.min(w) < 0):
             raise ValueError(f'{name}: edge weights must be finite and >= 0 (networkx computes with whatever it is '
                              f'given; a negative mutual weight has no meaning as a share of attention)')

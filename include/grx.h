@@ -33,8 +33,8 @@ extern "C" {
 #endif
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
-                                    grx_eccentricity and grx_structural_holes joined later under the same number (added
-                                    entry points only)
+                                    grx_eccentricity, grx_structural_holes and grx_weighted_distances joined later under
+                                    the same number (added entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -907,6 +907,48 @@ int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
                      int64_t n_hub_rows, int lanes_per_row, const int32_t *d_sources, int64_t n_sources, int words,
                      int32_t *d_source_ecc, int64_t *d_reach, int32_t *d_lower, int32_t *d_upper, int accumulate,
                      void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_weighted_distances: shortest-path distances by arc weight from many sources -- every source's
+ *   networkx.single_source_dijkstra_path_length(G, s, weight) -- and what closeness_centrality(G, distance=...),
+ *   harmonic_centrality(G, distance=...) and eccentricity(G, weight=...) compute from them.  The graph, the hub list,
+ *   the source list (int32 row ids, a repeated id counts once per occurrence, an id outside [0, n) is never written
+ *   through and reaches nothing) and the pulling direction are those of grx_distance_sums: pass the in-adjacency with
+ *   its weights to walk the out-arcs from each source.  d_w: fp64 per entry of d_col, the weight of that arc; NULL =
+ *   every weight is 1.  CONTRACT: every weight finite and >= 0 (the caller checks; parallel arcs are fine here -- the
+ *   lightest one wins -- and a self-loop never shortens a path).
+ *   For every node v and the sources s_0 .. s_{n_sources-1}, in that order:
+ *     reach[v]      = number of source occurrences s != v with a path s -> v
+ *     dsum[v]       = their distances d(s, v), added one by one from 0.0 in the order of d_sources
+ *     harmonic[v]   = fl(1 / d(s, v)) of those with d > 0, added likewise (networkx skips distance 0 as well)
+ *     far[v]        = the largest of those distances, 0.0 if there is none
+ *     source_ecc[b] = the largest finite d(s_b, v) over all v; 0.0 when s_b reaches nothing
+ *     dist[b * ld_dist + v] = d(s_b, v), +inf without a path (d_dist may be NULL; otherwise ld_dist >= n)
+ *   Method: a batched Bellman-Ford relaxation from +inf, S = `batch` sources at a time (16, 32 or 64; 0 = the library's
+ *   choice: the widest whose state fits 4 GiB, never below 16, no wider than the source list rounded up), S lanes per
+ *   node over fp64 state dist[v * S + b], Jacobi rounds over two buffers, a per-node stamp of the last round that
+ *   lowered it so that a row is stored only while it moves, device-steered rounds (8 per read-back) until one lowers
+ *   nothing; see the header of csrc/grx_sssp.hip.  State: 16 n S + 4 n bytes.  Work: every round gathers 8 S bytes
+ *   per arc; the number of rounds per batch is (the most arcs on any lightest path from its sources) + 1.  More than n + 1 rounds (a weight
+ *   outside the contract) return GRX_ERR_INVALID.
+ *   Exact: with weights >= 0 the distance is the minimum over the paths of the left-to-right fp64 sum of the weights,
+ *   which is what networkx's Dijkstra returns and the only fixed point of the relaxation: dist and source_ecc equal
+ *   networkx bit for bit.  The sums run in source order with no floating-point atomics, so every output has the same
+ *   bits for every `batch` and run; networkx adds the same terms in another order (closeness: its pop order;
+ *   harmonic: a set's), so dsum is equal for integer weights and both agree to 1e-12 relative otherwise.
+ *   d_reach: int64[n]; d_dsum, d_harmonic, d_far: fp64[n]; d_source_ecc: fp64[n_sources]; all overwritten.
+ *   h_rounds: HOST int64 or NULL: the rounds run, summed over the batches (reading it needs no extra wait: the call
+ *   waits for the stream once per 8 rounds anyway).  Returns GRX_ERR_INVALID before any HIP call for batch outside
+ *   {0, 16, 32, 64}, n outside [1, 2^31), n_sources < 0, d_dist with ld_dist < n and a short workspace.
+ *   d_workspace: grx_weighted_distances_workspace_bytes(n, batch, n_sources) bytes.
+ */
+size_t grx_weighted_distances_workspace_bytes(int64_t n, int batch, int64_t n_sources);
+int grx_weighted_distances(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
+                           const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                           const int32_t *d_sources, int64_t n_sources, int batch,
+                           int64_t *d_reach, double *d_dsum, double *d_harmonic, double *d_far,
+                           double *d_source_ecc, double *d_dist, int64_t ld_dist, int64_t *h_rounds,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
  * grx_biconnected: for every node of an undirected graph the number of biconnected components it belongs to -- what
