@@ -258,6 +258,11 @@ _SIGNATURES = {
     'grx_weighted_distances': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                        c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
+    'grx_weighted_betweenness_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
+    'grx_weighted_betweenness': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
+                                         c_double, c_int, c_void_p, POINTER(c_int64), POINTER(c_int64), c_void_p,
+                                         c_size_t, c_void_p]),
     'grx_biconnected_workspace_bytes': (c_size_t, [c_int64]),
     'grx_biconnected': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int64), c_void_p, c_size_t, c_void_p]),

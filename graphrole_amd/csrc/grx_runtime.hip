@@ -37,7 +37,8 @@ const char *const g_prof_names[GRX_K_COUNT] = {
     "nndsvd_apply_kernel", "nmf_w_pass_kernel", "reduce_partials_kernel", "nmf_h_update_kernel",
     "nmf_residual_kernel", "add_columns_kernel", "triangle_count_kernel", "egonet_from_triangles_kernel", "lloyd_max (scan+dp+lloyd+assign)",
     "key_bits_kernel", "sel_map_kernel", "sel_hist_kernel", "sel_walk1_kernel", "sel_collect_kernel", "sel_sort_kernel",
-    "sel_walk2_kernel", "role_rows_kernel", "sp_round_kernel (+hub)", "sp_finish_kernel (+source)"};
+    "sel_walk2_kernel", "role_rows_kernel", "sp_round_kernel (+hub)", "sp_finish_kernel (+source)",
+    "wbc relaxation: sp_round_kernel (+hub)", "wb_forward_kernel (+hub)", "wb_backward_kernel (+hub)"};
 }  // namespace
 
 static hipEvent_t prof_get_event()

@@ -35,7 +35,9 @@
 // (device-steered round loop, grx_common.h).  At most n - 1 rounds decrease something, so the loop refuses after
 // n + 1: weights outside the contract end in an error, not a hang.  Rows longer than GRX_HUB_FACTOR * lanes_per_row
 // are the CSR's hub list and get a workgroup each: its 256 / S lane groups take every (256 / S)-th arc and reduce
-// with fmin through LDS (min is order-free).
+// with fmin through LDS (min is order-free).  The relaxation itself -- pull_min, the source initialisation, the round
+// and hub-round kernels and the round loop sp_relax -- lives in grx_relax.h, which grx_weighted_betweenness.hip
+// includes as well.
 //
 // After the batch has converged one thread per node walks its S distances in source order and continues the running
 // values the batches before left: reach, dsum, harmonic and far are plain left-to-right sums / maxima in the order of
@@ -43,20 +45,14 @@
 // maximum, then an integer atomicMax on the fp64 bit pattern (non-negative doubles order as uint64).
 #pragma clang fp contract(off)
 
-#include "grx_common.h"
+#include "grx_relax.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int SP_BLOCK = 256;
-constexpr int SP_ROUND_BATCH = 8;                            // rounds enqueued between two read-backs
-constexpr int SP_MAX_ROW_BLOCKS = 8192;
 constexpr int SP_MAX_BLOCKS = 2048;                           // grid of the per-node launches
 constexpr size_t SP_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of S
-#define SP_INF __builtin_huge_val()
-
-bool valid_batch(int s) { return s == 16 || s == 32 || s == 64; }
 
 size_t state_bytes(int64_t n, int S) { return (size_t)(n > 0 ? n : 1) * ((size_t)S * 16 + 4); }
 
@@ -94,126 +90,6 @@ SpWs carve(void *base, int64_t n, int S)
     ws.stamp = reinterpret_cast<int32_t *>(p); p += grx_align_up(nn * 4, 256);
     ws.ctrl = reinterpret_cast<int32_t *>(p);
     return ws;
-}
-
-// min of `best` and fl(dist(u, lane) + w(u -> v)) over the arcs [b, e) with stride `step`; w == NULL: every weight
-// is 1
-template <int S>
-__device__ __forceinline__ double pull_min(int64_t b, int64_t e, int step, const int32_t *__restrict__ col,
-                                           const double *__restrict__ w, const double *__restrict__ D, int lane,
-                                           double best)
-{
-    int64_t j = b;
-    for (; j + 3 * step < e; j += 4 * step) {
-        const int64_t u0 = col[j], u1 = col[j + step], u2 = col[j + 2 * step], u3 = col[j + 3 * step];
-        const double w0 = w ? w[j] : 1.0, w1 = w ? w[j + step] : 1.0;
-        const double w2 = w ? w[j + 2 * step] : 1.0, w3 = w ? w[j + 3 * step] : 1.0;
-        const double c0 = D[u0 * S + lane] + w0, c1 = D[u1 * S + lane] + w1;
-        const double c2 = D[u2 * S + lane] + w2, c3 = D[u3 * S + lane] + w3;
-        best = fmin(best, fmin(fmin(c0, c1), fmin(c2, c3)));
-    }
-    for (; j < e; j += step) best = fmin(best, D[(int64_t)col[j] * S + lane] + (w ? w[j] : 1.0));
-    return best;
-}
-
-// lane b < count: dist(s_b, b) = 0 in both buffers, stamp(s_b) = 0 (one node may be the source of several lanes: each
-// lane has its own cell, and every stamp store carries the same value)
-template <int S>
-__global__ __launch_bounds__(SP_BLOCK) void sp_source_init_kernel(int64_t n, int count, const int32_t *__restrict__ src,
-                                                                  double *__restrict__ d0, double *__restrict__ d1,
-                                                                  int32_t *__restrict__ stamp,
-                                                                  int32_t *__restrict__ ctrl)
-{
-    const int b = threadIdx.x;
-    if (b < count) {
-        const int64_t s = src[b];
-        if (s >= 0 && s < n) {                              // an id outside [0, n) is never written through
-            d0[s * S + b] = 0.0;
-            d1[s * S + b] = 0.0;
-            stamp[s] = 0;
-        }
-    }
-    if (threadIdx.x == 0) { ctrl[GRX_CT_DONE] = 0; ctrl[GRX_CT_LEVEL] = 0; ctrl[GRX_CT_FOUND] = 0; }
-}
-
-// one round, rows up to hub_degree arcs: S lanes per node, SP_BLOCK / S nodes per workgroup and grid step
-template <int S>
-__global__ __launch_bounds__(SP_BLOCK) void sp_round_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
-                                                            const int32_t *__restrict__ col,
-                                                            const double *__restrict__ w, int64_t hub_degree,
-                                                            double *d0, double *d1, int32_t *stamp,
-                                                            int32_t *__restrict__ ctrl)
-{
-    constexpr int GROUPS = SP_BLOCK / S;
-    if (ctrl[GRX_CT_DONE]) return;
-    const int l = ctrl[GRX_CT_LEVEL];
-    const double *D = (l & 1) ? d1 : d0;
-    double *Dn = (l & 1) ? d0 : d1;
-    const int lane = threadIdx.x % S;
-    const int group_shift = threadIdx.x % GRX_WAVE / S * S;  // first lane of this node's group in its wavefront
-    const unsigned long long group_bits = S == GRX_WAVE ? ~0ull : (1ull << (S % GRX_WAVE)) - 1;
-    int found = 0;
-    // the trip count is the same in every lane of the workgroup: the ballot below sees every lane
-    for (int64_t first = (int64_t)blockIdx.x * GROUPS; first < n; first += (int64_t)gridDim.x * GROUPS) {
-        const int64_t v = first + threadIdx.x / S;
-        bool lower = false;
-        if (v < n) {
-            const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-            if (e - b <= hub_degree) {                      // longer rows: sp_round_hub_kernel
-                const int64_t cell = v * S + lane;
-                const double cur = D[cell];
-                const int own = stamp[v];
-                const double best = pull_min<S>(b, e, 1, col, w, D, lane, cur);
-                lower = best < cur;
-                if (lower || own >= l) Dn[cell] = best;
-            }
-        }
-        const unsigned long long moved = (__ballot(lower) >> group_shift) & group_bits;
-        if (moved && lane == 0) {
-            stamp[v] = l + 1;
-            found = 1;
-        }
-    }
-    if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[GRX_CT_FOUND] = 1;
-}
-
-// one round, hub rows: one workgroup per hub row; SP_BLOCK / S lane groups take every (SP_BLOCK / S)-th arc
-template <int S>
-__global__ __launch_bounds__(SP_BLOCK) void sp_round_hub_kernel(const int64_t *__restrict__ row_ptr,
-                                                                const int32_t *__restrict__ col,
-                                                                const double *__restrict__ w,
-                                                                const int32_t *__restrict__ hub_rows, double *d0,
-                                                                double *d1, int32_t *stamp,
-                                                                int32_t *__restrict__ ctrl)
-{
-    constexpr int GROUPS = SP_BLOCK / S;
-    __shared__ double part[SP_BLOCK];
-    if (ctrl[GRX_CT_DONE]) return;
-    const int l = ctrl[GRX_CT_LEVEL];
-    const double *D = (l & 1) ? d1 : d0;
-    double *Dn = (l & 1) ? d0 : d1;
-    const int t = threadIdx.x, lane = t % S;
-    const int64_t v = hub_rows[blockIdx.x];
-    part[t] = pull_min<S>(row_ptr[v] + t / S, row_ptr[v + 1], GROUPS, col, w, D, lane, SP_INF);
-    __syncthreads();
-#pragma unroll
-    for (int s = SP_BLOCK / 2; s >= S; s >>= 1) {          // part[t] for t < S: the minimum over every group
-        if (t < s) part[t] = fmin(part[t], part[t + s]);
-        __syncthreads();
-    }
-    if (t >= GRX_WAVE) return;
-    bool lower = false;
-    if (t < S) {
-        const int64_t cell = v * S + t;
-        const double cur = D[cell];
-        const double best = fmin(cur, part[t]);
-        lower = best < cur;
-        if (lower || stamp[v] >= l) Dn[cell] = best;
-    }
-    if (__ballot(lower) && t == 0) {                        // behind the stamp reads of its own wavefront
-        stamp[v] = l + 1;
-        ctrl[GRX_CT_FOUND] = 1;
-    }
 }
 
 // the converged batch, one thread per node: its `count` distances in source order continue the running values
@@ -306,31 +182,14 @@ template <int S>
 int run(const Args &a, const SpWs &ws, int64_t *rounds, hipStream_t st)
 {
     const int64_t n = a.n;
-    const unsigned row_blocks = grx_grid(n, SP_BLOCK / S, SP_MAX_ROW_BLOCKS);
-    const uint64_t inf_bits = (uint64_t)0x7ff << 52;
+    const SpPull g{n, a.row_ptr, a.col, a.w, a.hub_rows, a.n_hub_rows, a.hub_degree};
     for (int64_t first = 0; first < a.n_sources; first += S) {
         const int count = (int)std::min<int64_t>(S, a.n_sources - first);
-        grx_fill64(reinterpret_cast<uint64_t *>(ws.d0), n * S, inf_bits, st);
-        grx_fill64(reinterpret_cast<uint64_t *>(ws.d1), n * S, inf_bits, st);
-        grx_fill32(ws.stamp, n, -1, st);
-        sp_source_init_kernel<S><<<1, SP_BLOCK, 0, st>>>(n, count, a.sources + first, ws.d0, ws.d1, ws.stamp,
-                                                         ws.ctrl);
-        GRX_LAUNCH_CHECK();
-        int32_t h[2];
-        // at most n - 1 rounds lower a distance; one more finds that nothing moves
-        const int rc = grx_run_rounds(
+        const int rc = sp_relax<S>(
+            g, a.sources + first, count, ws.d0, ws.d1, ws.stamp, ws.ctrl,
             "grx_weighted_distances: the relaxation did not end after %lld rounds (a negative or NaN weight?)",
-            SP_ROUND_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
-                GRX_PROF(GRX_K_SSSP_ROUND, st);
-                if (a.n_hub_rows)
-                    sp_round_hub_kernel<S><<<(unsigned)a.n_hub_rows, SP_BLOCK, 0, st>>>(
-                        a.row_ptr, a.col, a.w, a.hub_rows, ws.d0, ws.d1, ws.stamp, ws.ctrl);
-                sp_round_kernel<S><<<row_blocks, SP_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.w, a.hub_degree, ws.d0,
-                                                                    ws.d1, ws.stamp, ws.ctrl);
-                return grx_frontier_advance(ws.ctrl, st);
-            });
+            GRX_K_SSSP_ROUND, rounds, st);
         if (rc != GRX_OK) return rc;
-        *rounds += (int64_t)h[GRX_CT_LEVEL] + 1;
         // the last round changed nothing: both buffers hold the fixed point
         GRX_PROF(GRX_K_SSSP_FINISH, st);
         sp_finish_kernel<S><<<grx_grid(n, SP_BLOCK, SP_MAX_BLOCKS), SP_BLOCK, 0, st>>>(
@@ -351,7 +210,7 @@ extern "C" {
 
 size_t grx_weighted_distances_workspace_bytes(int64_t n, int batch, int64_t n_sources)
 {
-    return ws_bytes(n, choose_batch(n, valid_batch(batch) ? batch : 0, n_sources));
+    return ws_bytes(n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources));
 }
 
 int grx_weighted_distances(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
@@ -360,7 +219,7 @@ int grx_weighted_distances(int64_t n, const int64_t *d_row_ptr, const int32_t *d
                            double *d_harmonic, double *d_far, double *d_source_ecc, double *d_dist, int64_t ld_dist,
                            int64_t *h_rounds, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    GRX_REQUIRE(batch == 0 || valid_batch(batch), "grx_weighted_distances: batch must be 0, 16, 32 or 64 (got %d)",
+    GRX_REQUIRE(batch == 0 || sp_valid_batch(batch), "grx_weighted_distances: batch must be 0, 16, 32 or 64 (got %d)",
                 batch);
     GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_weighted_distances: n = %lld out of range", (long long)n);
     GRX_REQUIRE(n_sources >= 0 && n_sources < (int64_t)1 << 31 && (n_sources == 0 || (d_sources && d_source_ecc)),

@@ -1320,6 +1320,31 @@ def weighted_distances(csr_pull: DeviceCSR, sources: np.ndarray, batch: int = 0,
     return reach, dsum, harmonic, far, source_ecc[:len(src)], dist, int(rounds.value)
 
 
+def _weighted_csr_args(csr: Optional[DeviceCSR]) -> tuple:
+    """(row_ptr, col, w, hub_rows, n_hubs, lanes_per_row) of a CSR with its weights as C arguments; nulls for None."""
+    if csr is None:
+        return (None, None, None, None, 0, 0)
+    return (_ptr(csr.row_ptr), _ptr(csr.col), _ptr(csr.w), _ptr(csr.hub_rows), csr.n_hubs, csr.lanes_per_row)
+
+
+def weighted_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.ndarray, endpoints: bool,
+                         scale: float, batch: int = 0) -> Tuple[torch.Tensor, int, int]:
+    """grx_weighted_betweenness: Brandes over shortest paths by arc weight from `sources` (internal row ids, in
+    accumulation order) over the out-adjacency csr_out and the in-adjacency csr_in (None for an undirected graph), each
+    with its weights .w (None: every arc counts 1; finite and > 0 otherwise); bc multiplied by `scale`.  batch = sources
+    per batch (16, 32 or 64; 0 = the library's choice).  (bc fp64[n], relaxation rounds summed over the batches, the
+    deepest level of the shortest-path DAG)."""
+    n = csr_out.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    ws, ws_bytes = _workspace('grx_weighted_betweenness_workspace_bytes', n, int(batch), len(src))
+    bc = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    rounds, levels = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call('grx_weighted_betweenness', n, *_weighted_csr_args(csr_out), *_weighted_csr_args(csr_in), _ptr(src),
+              len(src), int(bool(endpoints)), float(scale), int(batch), _ptr(bc), ctypes.byref(rounds),
+              ctypes.byref(levels), _ptr(ws), ws_bytes, _stream())
+    return bc, int(rounds.value), int(levels.value)
+
+
 def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor],
                                                                     Optional[torch.Tensor], int]:
     """grx_biconnected on the symmetric CSR of an undirected graph's distinct arcs: (count int64[n] = the number of

@@ -15,7 +15,11 @@ and directed form of effective size -- by the per-arc row intersections of csrc/
 mutual-weight CSR, the first measures here besides ``weighted_degree``, ``pagerank`` and ``eigenvector`` that read an
 edge weight, and -- with ``node_measures(..., distance='weight')`` -- closeness, harmonic centrality and eccentricity
 over shortest paths by edge weight, together with the distances themselves (``dijkstra_path_lengths``), by the batched
-Bellman-Ford relaxation of csrc/grx_sssp.hip, whose fixed point is networkx's Dijkstra distance bit for bit.
+Bellman-Ford relaxation of csrc/grx_sssp.hip, whose fixed point is networkx's Dijkstra distance bit for bit, and --
+with ``weighted_betweenness_centrality`` or ``node_measures(..., betweenness_weight='weight')`` -- betweenness
+centrality over those shortest paths by csrc/grx_weighted_betweenness.hip: the same relaxation, the shortest-path DAG
+read off its converged distances (arc u -> v is on a lightest path iff fl(D(u) + w) == D(v) and D(u) < D(v), networkx's
+own test of equally short), and Brandes' two passes in the order of the depth in that DAG, with no priority queue.
 """
 from __future__ import annotations
 
@@ -115,7 +119,7 @@ def _count_csrs(graph, K, host):
 def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                   max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
                   endpoints: bool = False, wf_improved: bool = True, weight=None,
-                  distance=None) -> pd.DataFrame:
+                  distance=None, betweenness_weight=None) -> pd.DataFrame:
     """
     Node x measure table of well-known graph measures, computed on the GPU.
 
@@ -135,15 +139,20 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       missing attribute counts 1), as networkx's ``distance='weight'`` resp. ``weight='weight'``: all three come from
       one pass of grx_weighted_distances with every node a source, and ``'eccentricity'`` is then a float64 column.
       It applies to these three columns only
+    :param betweenness_weight: None = ``'betweenness_centrality'`` counts hops; ``'weight'`` = the column is
+      ``weighted_betweenness_centrality`` (shortest paths by the edge attribute ``'weight'``, a missing attribute counts
+      1) with the same `k`, `seed`, `normalized` and `endpoints`; ``.attrs['weighted_betweenness']`` then holds its
+      ``rounds`` and ``levels``.  It applies to that column only
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
-    :raises ValueError: an unknown measure name; ``distance='weight'`` with a negative, NaN or infinite edge weight
+    :raises ValueError: an unknown measure name; ``distance='weight'`` with a negative, NaN or infinite edge weight;
+      ``betweenness_weight='weight'`` with a weight that is not finite and > 0
     :raises NotImplementedError: a measure that networkx does not implement for this kind of graph (among them
       ``'biconnected_components'`` and ``'onion_layer'`` of a directed graph, and ``'core_number'`` and
       ``'onion_layer'`` of a multigraph or of a graph with a self-loop), or that is outside this implementation's scope
       (directed / multigraph clustering and effective size -- ``effective_size(G)`` computes the directed and the
       weighted form --, ``'constraint'`` of a multigraph, weighted distances of a multigraph or of a graph with
-      parallel edges, a `distance` other than None and ``'weight'``)
+      parallel edges, a `distance` or `betweenness_weight` other than None and ``'weight'``)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
     :raises networkx.NetworkXError: ``'eccentricity'`` of a graph that is not (strongly) connected, as networkx
 
@@ -152,12 +161,13 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     """
     return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter, k=k, seed=seed,
                        normalized=normalized, endpoints=endpoints, wf_improved=wf_improved, weight=weight,
-                       distance=distance)
+                       distance=distance, betweenness_weight=betweenness_weight)
 
 
 def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                 max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
-                endpoints: bool = False, wf_improved: bool = True, weight=None, distance=None) -> pd.DataFrame:
+                endpoints: bool = False, wf_improved: bool = True, weight=None, distance=None,
+                betweenness_weight=None) -> pd.DataFrame:
     """``node_measures`` on an existing graph adapter (its device CSR is built once and reused)."""
     directed = bool(graph.directed)
     multi = bool(getattr(graph, '_multi', False))
@@ -172,8 +182,12 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             why = _unavailable(nm, directed, multi)
             if why is not None:
                 raise NotImplementedError(why)
+    by_weight_bc = False
     if 'betweenness_centrality' in names:
         sources = _betweenness_sources(graph, k, seed)        # argument errors before any device work
+        if _weight_flag('betweenness_centrality', betweenness_weight):
+            _weighted_betweenness_refusals(graph, "node_measures(G, ..., betweenness_weight='weight')")
+            by_weight_bc = True
     peeled = [nm for nm in names if nm in ('core_number', 'onion_layer')]
     if peeled:
         _peeling_refusals(graph, peeled[0])                   # likewise: read from the host CSR
@@ -249,6 +263,16 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             if 'constraint' not in cache:
                 cache['constraint'] = _structural_holes(graph, K, weighted, True, False)[0]
             col, dt = cache['constraint'], np.dtype('float64')
+        elif nm == 'betweenness_centrality' and by_weight_bc:
+            if 'weighted_betweenness' not in cache:
+                # shortest paths by weight: the weighted CSRs, out for the backward pass and (directed) in for the
+                # relaxation and the forward pass
+                if directed:
+                    _weighted_pull(graph, 'weighted betweenness centrality')
+                cache['weighted_betweenness'] = K.weighted_betweenness(
+                    out, tr if directed else None, np.asarray(host.inv)[sources], endpoints,
+                    _rescale_factor(host.n, normalized, directed, k, endpoints))
+            col, dt = cache['weighted_betweenness'][0], np.dtype('float64')
         elif nm == 'betweenness_centrality':
             # BFS walks G[v]: the distinct arcs, out and (directed) in, not a neighbour multiset
             s_out, s_in = _structure_pair(graph, 'betweenness_centrality')
@@ -292,6 +316,9 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
         dtypes.append(dt)
     frame = graph._frame(names, cols, dtypes)
     frame.attrs['iterations'] = iterations
+    if 'weighted_betweenness' in cache:
+        frame.attrs['weighted_betweenness'] = dict(rounds=cache['weighted_betweenness'][1],
+                                                   levels=cache['weighted_betweenness'][2])
     return frame
 
 
@@ -355,7 +382,8 @@ def betweenness_centrality(G, k: Optional[int] = None, normalized: bool = True, 
     :param k: None = every node is a source, in the graph's own node order (``list(G)``, igraph vertex order, CSRGraph
       row order); otherwise ``seed.sample(list(nodes), k)`` sources in the sampled order, and the sums scaled by n / k
     :param normalized, endpoints: as networkx
-    :param weight: must be None (weighted betweenness is Dijkstra's algorithm, not implemented here)
+    :param weight: must be None here; ``weighted_betweenness_centrality(G, weight='weight')`` computes betweenness
+      over shortest paths by weight
     :param seed: int (``random.Random(seed)``), None (the global state of ``random``, as networkx) or ``random.Random``
     :return: float64 Series indexed by the sorted node labels (the index of ``node_measures``)
     :raises NotImplementedError: weight is not None
@@ -367,10 +395,64 @@ def betweenness_centrality(G, k: Optional[int] = None, normalized: bool = True, 
     as seed raises TypeError (networkx accepts it).
     """
     if weight is not None:
-        raise NotImplementedError(f'weighted betweenness (nx.betweenness_centrality(G, weight={weight!r})) is '
-                                  f'Dijkstra-based and not implemented here; use networkx')
+        raise NotImplementedError(f'weighted betweenness (nx.betweenness_centrality(G, weight={weight!r})) walks '
+                                  f'shortest paths by weight, which this function does not; '
+                                  f"weighted_betweenness_centrality(G, weight='weight') computes it")
     frame = node_measures(G, ['betweenness_centrality'], k=k, seed=seed, normalized=normalized, endpoints=endpoints)
     return frame['betweenness_centrality']
+
+
+def _weighted_betweenness_refusals(graph, what: str) -> None:
+    """What betweenness by weight refuses, read from the host edge arrays: no device work."""
+    if _has_parallel_edges(graph):
+        raise NotImplementedError(f'{what}: shortest paths by weight are not computed on a multigraph or a graph with '
+                                  f'parallel edges (their weights are summed into one arc here, where Dijkstra takes '
+                                  f'the lightest); merge the parallel edges first')
+    w = _host_arcs(graph.to_csr())[2]
+    if w is not None and len(w) and (not np.all(np.isfinite(w)) or np.min(w) <= 0):
+        raise ValueError(f'{what}: edge weights must be finite and > 0 (a zero weight makes networkx count paths '
+                         f'through nodes it has already settled, so its own result depends on the order of its heap; '
+                         f'a negative, NaN or infinite weight defines no shortest path)')
+
+
+def weighted_betweenness_centrality(G, k: Optional[int] = None, normalized: bool = True, weight='weight',
+                                    endpoints: bool = False, seed=None) -> pd.Series:
+    """
+    Betweenness centrality over shortest paths by edge weight on the GPU: networkx 3.4.2's
+    ``betweenness_centrality(G, k, normalized, weight='weight', endpoints, seed)`` (Brandes' algorithm with one
+    Dijkstra search per source) restated without a priority queue by csrc/grx_weighted_betweenness.hip, up to 64
+    sources per batch.  The Bellman-Ford relaxation of ``dijkstra_path_lengths`` gives networkx's distances D bit for
+    bit; the arc u -> v of weight w lies on a lightest path iff ``D[u] + w == D[v]`` as doubles -- networkx's own test
+    of "equally short" -- and ``D[u] < D[v]``; the path counts and the dependencies then run over that DAG in the order
+    of its depth.
+
+    :param G: any graph ``node_measures`` accepts, without parallel edges; self-loops never lie on a shortest path
+    :param k, normalized, endpoints, seed: as ``betweenness_centrality``: the same sources, in the same order, and the
+      same scale
+    :param weight: ``'weight'`` = the edge attribute the adapters read (a ``CSRGraph``'s weight array; a missing
+      attribute counts 1); None = ``betweenness_centrality(G, ...)``, the unweighted kernel
+    :return: float64 Series named ``betweenness_centrality`` indexed by the sorted node labels; ``.attrs['rounds']``
+      holds the relaxation rounds run (summed over the batches of sources) and ``.attrs['levels']`` the deepest level
+      of any source's shortest-path DAG (the most arcs on a lightest path)
+    :raises ValueError: a weight that is not finite and > 0; k outside 1..n.  A zero weight is refused because
+      networkx then counts paths through nodes it has already settled: its own result depends on the order of its heap
+    :raises NotImplementedError: a multigraph or parallel edges; another `weight` (a different attribute name, a
+      callable); G is directed and its adapter has no in-adjacency
+    :raises TypeError: a seed of another type
+
+    Values agree with networkx to 1e-12 relative -- only the order of the additions inside one source's dependency
+    delta(v) differs -- and the entries networkx has at exactly 0 are exactly 0.  Stated divergences: those of
+    ``betweenness_centrality``; zero weights raise; an edge whose weight is absorbed by the distance before it
+    (``d + w == d`` in fp64, e.g. 1e-17 after 1.0) is not a shortest-path edge here, where networkx's answer depends on
+    its heap order.
+    """
+    if not _weight_flag('betweenness_centrality', weight):
+        return betweenness_centrality(G, k=k, normalized=normalized, endpoints=endpoints, seed=seed)
+    frame = node_measures(G, ['betweenness_centrality'], k=k, seed=seed, normalized=normalized, endpoints=endpoints,
+                          betweenness_weight='weight')
+    series = frame['betweenness_centrality']
+    series.attrs = dict(frame.attrs['weighted_betweenness'])
+    return series
 
 
 def _rows_of(graph, nodes) -> np.ndarray:

@@ -33,8 +33,8 @@ extern "C" {
 #endif
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
-                                    grx_eccentricity, grx_structural_holes and grx_weighted_distances joined later under
-                                    the same number (added entry points only)
+                                    grx_eccentricity, grx_structural_holes, grx_weighted_distances and
+                                    grx_weighted_betweenness joined later under the same number (added entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -949,6 +949,48 @@ int grx_weighted_distances(int64_t n, const int64_t *d_row_ptr, const int32_t *d
                            int64_t *d_reach, double *d_dsum, double *d_harmonic, double *d_far,
                            double *d_source_ecc, double *d_dist, int64_t ld_dist, int64_t *h_rounds,
                            void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_weighted_betweenness restates networkx.betweenness_centrality(G, k, normalized, weight, endpoints, seed) for a
+ *   weight attribute (betweenness.py: _single_source_dijkstra_path_basic, _accumulate_basic / _accumulate_endpoints,
+ *   _rescale) for the sources d_sources[0 .. n_sources) (int32 row ids, distinct or not, an id outside [0, n) reaches
+ *   nothing) in that order, without a priority queue.  Per batch of S sources: the relaxation of
+ *   grx_weighted_distances gives networkx's Dijkstra distances D bit for bit; arc u -> v of weight w lies on a lightest
+ *   path from a source iff D(v) is finite, fl(D(u) + w) == D(v) and D(u) < D(v) (networkx's own equality of fp64 sums;
+ *   the strict inequality keeps the relation acyclic); a device-steered round loop gives every reached node its depth in
+ *   that DAG and sigma = the sum of its predecessors' sigma once ALL of them are resolved (pulled over the in-adjacency);
+ *   then deepest level first delta(v) = sum over the DAG successors x of sigma(v) * coeff(x), coeff(x) = (1 + delta(x))
+ *   / sigma(x) (pulled over the out-adjacency); bc[w] += delta(w) for every reached w != s (endpoints: += delta(w) + 1,
+ *   and bc[s] += reached - 1).  Finally bc *= scale (the caller computes _rescale's factor, 1 for none).
+ *   d_row_ptr / d_col / d_w: the out-adjacency with its fp64 weights; d_in_row_ptr / d_in_col / d_in_w: the
+ *   in-adjacency (transposed CSR) with its weights of a directed graph, d_in_row_ptr NULL for an undirected one (the out
+ *   CSR then serves both passes).  d_w NULL = every weight is 1 (then d_in_w NULL as well).  CONTRACT: every weight
+ *   finite and > 0 (the caller checks).  A zero weight would let networkx count paths through nodes it has already
+ *   settled, so its own result depends on its heap order; here an arc whose weight is absorbed (fl(d + w) == d) or zero
+ *   is not a shortest-path arc, and a node reached only through such arcs counts as not reached: stated divergences.
+ *   Rows longer than GRX_HUB_FACTOR * lanes_per_row (resp. in_lanes_per_row) must be listed in d_hub_rows (resp.
+ *   d_in_hub_rows).  batch: S = 16, 32 or 64; 0 = the library's choice: the widest whose state fits 4 GiB, never below
+ *   16, no wider than the source list rounded up.  State: 28 n S + 4 n bytes (two distance buffers -- the second
+ *   becomes delta once the relaxation has converged --, sigma, depth, the relaxation's stamps).
+ *   Bound: sigma must stay below 2^53.  Deterministic and the same bits for every S and run: bc[v] adds its sources'
+ *   terms one source after another in the order of d_sources, hub rows combine four partial sums in a fixed order for
+ *   every S, no floating-point atomics.  Against networkx only the order of the additions inside one delta(v)
+ *   differs, so results agree to 1e-12 relative and entries networkx has at exactly 0 are exactly 0.
+ *   d_bc: fp64[n], overwritten.  h_rounds: HOST int64 or NULL: the relaxation rounds run, summed over the batches;
+ *   h_levels: HOST int64 or NULL: the deepest DAG level of any batch (with unit weights: the BFS depth).  Returns
+ *   GRX_ERR_INVALID before any HIP call for batch outside {0, 16, 32, 64}, n outside [1, 2^31), a bad source list, hub
+ *   list or lanes_per_row, null pointers and a short workspace; and when the relaxation or the forward pass runs more
+ *   than n + 1 rounds (weights outside the contract): an error, never a hang.
+ *   d_workspace: grx_weighted_betweenness_workspace_bytes(n, batch, n_sources) bytes.
+ */
+size_t grx_weighted_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources);
+int grx_weighted_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
+                             const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                             const int64_t *d_in_row_ptr, const int32_t *d_in_col, const double *d_in_w,
+                             const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
+                             const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch,
+                             double *d_bc, int64_t *h_rounds, int64_t *h_levels, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
 
 /*
  * grx_biconnected: for every node of an undirected graph the number of biconnected components it belongs to -- what
