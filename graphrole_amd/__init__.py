@@ -16,7 +16,8 @@ def __getattr__(name):
     if name in ('node_measures', 'betweenness_centrality', 'closeness_centrality', 'harmonic_centrality',
                 'biconnected_component_counts', 'articulation_points', 'biconnected_components', 'core_number',
                 'onion_layers', 'eccentricity', 'diameter', 'radius', 'center', 'periphery', 'constraint',
-                'effective_size', 'dijkstra_path_lengths', 'weighted_betweenness_centrality', 'ConvergenceError'):
+                'effective_size', 'dijkstra_path_lengths', 'weighted_betweenness_centrality', 'clustering',
+                'average_clustering', 'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     raise AttributeError(name)

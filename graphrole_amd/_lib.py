@@ -272,6 +272,9 @@ _SIGNATURES = {
     'grx_structural_holes_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'grx_structural_holes': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'grx_clustering_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'grx_clustering': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -20,6 +20,9 @@ HUB_FACTOR = 32          # GRX_HUB_FACTOR in csrc/grx_common.h
 SH_BLOCK = 256           # csrc/grx_structural_holes.hip: threads per workgroup,
 SH_ROW_MAX_WG = 2048     # workgroups of its row kernels (256 / lanes rows per workgroup pass)
 SH_ARC_MAX_WG = 8192     # and of its per-arc kernel (256 / lanes arcs per workgroup pass)
+CL_BLOCK = 256           # csrc/grx_clustering.hip: the same three constants
+CL_ROW_MAX_WG = 2048
+CL_ARC_MAX_WG = 8192
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1409,3 +1412,24 @@ def structural_holes(csr: DeviceCSR, z: Optional[torch.Tensor] = None, out_row_p
     _lib.call('grx_structural_holes', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(z), hub_ptr, n_hubs, lanes_per_row,
               _ptr(out_row_ptr), _ptr(con), _ptr(es), _ptr(loc), _ptr(ws), ws_bytes, _stream())
     return con, es, loc
+
+
+def clustering(csr: DeviceCSR, fwd: Optional[torch.Tensor] = None, bwd: Optional[torch.Tensor] = None,
+               max_weight: float = 1.0, want_triangles: bool = False,
+               lanes: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """grx_clustering on a structurally symmetric CSR: (clustering fp64[n], t fp64[n] -- the numerator, twice
+    networkx's weighted_triangles resp. its directed_triangles -- or None).  fwd, bwd: fp64[nnz] device tensors, at arc
+    (u, v) the weights of u -> v and of v -> u, a negative value for an absent direction; bwd=None: an undirected graph;
+    fwd=None: an undirected graph without weights (csr.w is NOT read unless passed here).  max_weight: the largest
+    weight of any edge, self-loops included.  lanes = lanes per row and per arc (4, 8, 16 or 32; None =
+    csr.lanes_per_row), with the hub list of that width."""
+    if fwd is None and bwd is not None:
+        raise ValueError('clustering: bwd without fwd')
+    n = csr.n
+    ws, ws_bytes = _workspace('grx_clustering_workspace_bytes', n, csr.nnz)
+    cl = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    tri = torch.empty(max(n, 1), dtype=torch.float64, device=device()) if want_triangles else None
+    hub_ptr, n_hubs, lanes_per_row, _keep = _hubs_for(csr, lanes)
+    _lib.call('grx_clustering', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(fwd), _ptr(bwd), float(max_weight), hub_ptr,
+              n_hubs, lanes_per_row, _ptr(cl), _ptr(tri), _ptr(ws), ws_bytes, _stream())
+    return cl, tri

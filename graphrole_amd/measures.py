@@ -19,11 +19,17 @@ Bellman-Ford relaxation of csrc/grx_sssp.hip, whose fixed point is networkx's Di
 with ``weighted_betweenness_centrality`` or ``node_measures(..., betweenness_weight='weight')`` -- betweenness
 centrality over those shortest paths by csrc/grx_weighted_betweenness.hip: the same relaxation, the shortest-path DAG
 read off its converged distances (arc u -> v is on a lightest path iff fl(D(u) + w) == D(v) and D(u) < D(v), networkx's
-own test of equally short), and Brandes' two passes in the order of the depth in that DAG, with no priority queue.
+own test of equally short), and Brandes' two passes in the order of the depth in that DAG, with no priority queue,
+and -- with ``clustering`` / ``average_clustering`` or ``node_measures(..., clustering_weight='weight')`` -- the
+clustering coefficient of a directed graph (Fagiolo) and of a graph with weights (Onnela's geometric mean of the
+normalised triangle weights), as networkx's ``clustering(G, nodes, weight)`` defines them, by
+csrc/grx_clustering.hip: the cube root of every normalised weight once per arc, then the per-arc row intersections of
+the structural-hole kernel over the all-neighbours CSR.
 """
 from __future__ import annotations
 
 import copy
+import math
 import random
 from numbers import Integral
 from typing import List, Optional, Sequence
@@ -71,8 +77,10 @@ def _unavailable(name: str, directed: bool, multi: bool) -> Optional[str]:
         if multi and name == 'clustering':
             return f'networkx does not implement {CATALOGUE[name]} for a multigraph'
         if directed or multi:
+            also = ('; clustering(G) of this package computes the directed form' if name == 'clustering' and not multi
+                    else '')
             return (f'{name} of a {kind} is not computed here (only undirected graphs without parallel edges); '
-                    f'use {CATALOGUE[name]} from networkx')
+                    f'use {CATALOGUE[name]} from networkx{also}')
     if name == 'constraint' and multi:
         return (f'{name} of a {kind} is not computed here (networkx adds key dictionaries there, not weights: its '
                 f'result on a multigraph is not meaningful); merge the parallel edges first')
@@ -119,7 +127,7 @@ def _count_csrs(graph, K, host):
 def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                   max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
                   endpoints: bool = False, wf_improved: bool = True, weight=None,
-                  distance=None, betweenness_weight=None) -> pd.DataFrame:
+                  distance=None, betweenness_weight=None, clustering_weight=None) -> pd.DataFrame:
     """
     Node x measure table of well-known graph measures, computed on the GPU.
 
@@ -143,16 +151,21 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
       ``weighted_betweenness_centrality`` (shortest paths by the edge attribute ``'weight'``, a missing attribute counts
       1) with the same `k`, `seed`, `normalized` and `endpoints`; ``.attrs['weighted_betweenness']`` then holds its
       ``rounds`` and ``levels``.  It applies to that column only
+    :param clustering_weight: None = ``'clustering'`` is the coefficient of an undirected graph without weights, as it
+      always was; ``'weight'`` = the column is ``clustering(G, weight='weight')``: the weighted form, of an undirected or
+      of a directed graph (a missing attribute counts 1).  It applies to that column only
     :return: DataFrame indexed by the sorted node labels (the index of ``extract_features()``);
       ``.attrs['iterations']`` holds the power-iteration counts
     :raises ValueError: an unknown measure name; ``distance='weight'`` with a negative, NaN or infinite edge weight;
-      ``betweenness_weight='weight'`` with a weight that is not finite and > 0
+      ``betweenness_weight='weight'`` with a weight that is not finite and > 0; ``clustering_weight='weight'`` with a
+      negative or non-finite weight, or with weights that are all zero
     :raises NotImplementedError: a measure that networkx does not implement for this kind of graph (among them
       ``'biconnected_components'`` and ``'onion_layer'`` of a directed graph, and ``'core_number'`` and
       ``'onion_layer'`` of a multigraph or of a graph with a self-loop), or that is outside this implementation's scope
-      (directed / multigraph clustering and effective size -- ``effective_size(G)`` computes the directed and the
-      weighted form --, ``'constraint'`` of a multigraph, weighted distances of a multigraph or of a graph with
-      parallel edges, a `distance` or `betweenness_weight` other than None and ``'weight'``)
+      (directed / multigraph clustering and effective size -- ``effective_size(G)`` and ``clustering(G)`` compute the
+      directed and the weighted forms, and ``clustering_weight='weight'`` brings the latter into this table --,
+      ``'constraint'`` of a multigraph, weighted distances of a multigraph or of a graph with
+      parallel edges, a `distance`, `betweenness_weight` or `clustering_weight` other than None and ``'weight'``)
     :raises ConvergenceError: PageRank or eigenvector centrality did not converge within max_iter iterations
     :raises networkx.NetworkXError: ``'eccentricity'`` of a graph that is not (strongly) connected, as networkx
 
@@ -161,13 +174,13 @@ def node_measures(G, measures: Optional[Sequence[str]] = None, *, alpha: float =
     """
     return measures_of(_adapter(G), measures, alpha=alpha, tol=tol, max_iter=max_iter, k=k, seed=seed,
                        normalized=normalized, endpoints=endpoints, wf_improved=wf_improved, weight=weight,
-                       distance=distance, betweenness_weight=betweenness_weight)
+                       distance=distance, betweenness_weight=betweenness_weight, clustering_weight=clustering_weight)
 
 
 def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float = 0.85, tol: float = 1e-6,
                 max_iter: int = 100, k: Optional[int] = None, seed=None, normalized: bool = True,
                 endpoints: bool = False, wf_improved: bool = True, weight=None, distance=None,
-                betweenness_weight=None) -> pd.DataFrame:
+                betweenness_weight=None, clustering_weight=None) -> pd.DataFrame:
     """``node_measures`` on an existing graph adapter (its device CSR is built once and reused)."""
     directed = bool(graph.directed)
     multi = bool(getattr(graph, '_multi', False))
@@ -178,10 +191,15 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
         unknown = [nm for nm in names if nm not in CATALOGUE]
         if unknown:
             raise ValueError(f'unknown measure(s) {unknown}; the catalogue is {list(CATALOGUE)}')
+    # the weighted clustering column is defined for directed graphs too: its own refusals stand in for _unavailable
+    by_weight_cl = 'clustering' in names and _weight_flag('clustering', clustering_weight)
+    if measures is not None:
         for nm in names:
-            why = _unavailable(nm, directed, multi)
+            why = None if (nm == 'clustering' and by_weight_cl) else _unavailable(nm, directed, multi)
             if why is not None:
                 raise NotImplementedError(why)
+    if by_weight_cl:
+        _clustering_refusals(graph, True)                     # argument errors before any device work
     by_weight_bc = False
     if 'betweenness_centrality' in names:
         sources = _betweenness_sources(graph, k, seed)        # argument errors before any device work
@@ -255,6 +273,10 @@ def measures_of(graph, measures: Optional[Sequence[str]] = None, *, alpha: float
             col, dt = counts('in'), np.dtype('int64')
         elif nm == 'out_degree':
             col, dt = counts('out'), np.dtype('int64')
+        elif nm == 'clustering' and by_weight_cl:
+            if 'weighted_clustering' not in cache:
+                cache['weighted_clustering'] = _clustering_column(graph, K, True)
+            col, dt = cache['weighted_clustering'], np.dtype('float64')
         elif nm == 'clustering':
             col, dt = local()[0], np.dtype('float64')
         elif nm == 'effective_size':
@@ -1175,3 +1197,127 @@ def effective_size(G, nodes=None, weight=None) -> pd.Series:
     raises: this function is the way in.
     """
     return _structural_hole_series(G, 'effective_size', nodes, weight)
+
+
+# ------------------------------------------------------------------------------- weighted and directed clustering
+def _clustering_refusals(graph, weighted: bool) -> None:
+    """What clustering refuses, read from the host edge arrays: no device work."""
+    if _has_parallel_edges(graph):
+        raise NotImplementedError(f'networkx does not implement {CATALOGUE["clustering"]} for a multigraph, and parallel '
+                                  f'edges are merged into one arc here; merge the parallel edges first')
+    if weighted:
+        w = _host_arcs(graph.to_csr())[2]
+        if w is not None and len(w):
+            if not np.all(np.isfinite(w)) or np.min(w) < 0:
+                raise ValueError('clustering: edge weights must be finite and >= 0 (the weight of a triangle is the '
+                                 'cube root of the product of its three normalised weights)')
+            if np.max(w) == 0:
+                raise ValueError('clustering: every edge weight is 0, so the weights cannot be divided by their maximum '
+                                 '(networkx raises ZeroDivisionError)')
+
+
+def _max_weight(graph, weighted: bool) -> float:
+    """networkx's max_weight: the largest weight of any edge, self-loops included; 1 without weights or edges."""
+    w = _host_arcs(graph.to_csr())[2] if weighted else None
+    return float(np.max(w)) if w is not None and len(w) else 1.0
+
+
+def _directional_csr(graph, K, weighted: bool):
+    """(device CSR, fwd, bwd) of grx_clustering for a directed graph: the structurally symmetric CSR of networkx's
+    all_neighbors in internal row order, with the weight of u -> v (fwd) and of v -> u (bwd) at arc (u, v), -1 where
+    that direction is absent; without `weighted` a present direction is 1.  Cached on the adapter per `weighted`."""
+    cache = graph.__dict__.setdefault('_directional', {})
+    if weighted in cache:
+        return cache[weighted]
+    host = graph._device_graph()[0]
+    g = graph.to_csr()
+    src, dst, w = _host_arcs(g)
+    n = g.n
+    inv = np.asarray(host.inv, dtype=np.int64)
+    a, b = inv[np.asarray(src, dtype=np.int64)], inv[np.asarray(dst, dtype=np.int64)]
+    vals = np.ones(len(a)) if (w is None or not weighted) else np.asarray(w, dtype=np.float64)
+    key, inverse = np.unique(np.concatenate([a, b]) * np.int64(max(n, 1)) + np.concatenate([b, a]),
+                             return_inverse=True)
+    inverse = inverse.ravel()
+    fwd = np.full(len(key), -1.0)
+    bwd = np.full(len(key), -1.0)
+    fwd[inverse[:len(a)]] = vals                                # arc (u, v) as given
+    bwd[inverse[len(a):]] = vals                                # and seen from its head
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=row_ptr[1:])
+    csr = K.DeviceCSR(row_ptr, (key % max(n, 1)).astype(np.int32), fwd)
+    cache[weighted] = (csr, csr.w, K.to_device(bwd if len(bwd) else np.zeros(1)))
+    return cache[weighted]
+
+
+def _clustering_column(graph, K, weighted: bool):
+    """The device column of grx_clustering in internal row order (not the undirected graph without weights, which is
+    the triangle-count column)."""
+    if graph.directed:
+        csr, fwd, bwd = _directional_csr(graph, K, weighted)
+    else:
+        csr = graph._device_graph()[1]
+        fwd, bwd = (csr.w if weighted else None), None
+    return K.clustering(csr, fwd, bwd, _max_weight(graph, weighted and fwd is not None))[0]
+
+
+def clustering(G, nodes=None, weight=None) -> pd.Series:
+    """
+    The clustering coefficient of every node on the GPU -- how many of the triangles a node could close with its
+    neighbours exist, by weight and by direction: ``nx.clustering(G, nodes, weight)`` of networkx 3.4.2 (cluster.py) in
+    its four forms.  For an undirected graph with ``weight=None`` it is the ``'clustering'`` column of
+    ``node_measures`` unchanged (triangle counts); a directed graph (Fagiolo's coefficient), a `weight` (Onnela's
+    geometric mean of the three normalised weights of each triangle) or both go through grx_clustering
+    (csrc/grx_clustering.hip): with s(u, v) = cbrt(w(u -> v) / max_weight) + cbrt(w(v -> u) / max_weight) over the
+    neighbours in either direction, t(u) = sum_v s(u, v) sum_w s(u, w) s(v, w) over the triangles (u, v, w), divided by
+    d (d - 1) resp. 2 (dt (dt - 1) - 2 db).
+
+    :param G: any graph ``node_measures`` accepts, undirected or directed; self-loops are ignored, as networkx
+    :param nodes: None = every node; otherwise an iterable of nodes
+    :param weight: None = every edge counts 1; ``'weight'`` = the edge attribute the adapters read (a ``CSRGraph``'s
+      weight array; a missing attribute counts 1).  Every weight is divided by the largest one, self-loops included
+    :return: float64 Series named ``clustering`` indexed by the sorted node labels (the index of ``node_measures``) or
+      by the sorted members of `nodes`
+    :raises NotImplementedError: another `weight` (a different attribute name, a callable); a multigraph or parallel
+      edges (networkx: not implemented for multigraphs)
+    :raises ValueError: a negative or non-finite weight; weights that are all zero
+    :raises KeyError: a member of `nodes` is not a node
+
+    Without weights the result equals networkx bit for bit, directed or not (every quantity is an integer), and
+    constant weights give those same bits.  Otherwise values agree with networkx to 1e-12 relative: the cube root is
+    taken per arc and the three roots are multiplied, where networkx multiplies three quotients and takes one root, and
+    the sums run in another order.  Stated divergences: `weight` is None or ``'weight'``; negative and non-finite
+    weights raise (networkx computes with them); weights that are all zero raise ValueError (networkx:
+    ZeroDivisionError); a zero result is the float 0.0 (networkx: the int 0); weights so small that networkx's product
+    of three normalised weights underflows are outside the comparison.  ``triangles`` of a directed graph,
+    ``transitivity``, ``square_clustering`` and ``generalized_degree`` are not offered.
+    """
+    weighted = _weight_flag('clustering', weight)
+    graph = _adapter(G)
+    _clustering_refusals(graph, weighted)
+    rows = _member_rows(graph, nodes)
+    if not graph.directed and not weighted:
+        series = measures_of(graph, ['clustering'])['clustering']      # the triangle-count column, unchanged
+    elif graph.to_csr().n == 0:
+        series = pd.Series([], index=pd.Index([]), dtype=np.float64, name='clustering')
+    else:
+        col = _clustering_column(graph, graph._K(), weighted)
+        series = graph._frame(['clustering'], [col], [np.dtype('float64')])['clustering']
+    return series if rows is None else series.iloc[rows]
+
+
+def average_clustering(G, nodes=None, weight=None, count_zeros: bool = True) -> float:
+    """
+    ``nx.average_clustering(G, nodes, weight, count_zeros)``: the mean of ``clustering(G, nodes, weight)`` on the host;
+    with ``count_zeros=False`` the mean of its non-zero values.
+
+    :raises ZeroDivisionError: there is no value to average (no node; with ``count_zeros=False`` no non-zero value), as
+      networkx
+    :raises NotImplementedError, ValueError, KeyError: as ``clustering``
+    """
+    values = clustering(G, nodes=nodes, weight=weight).to_numpy()
+    if not count_zeros:
+        values = values[values != 0]
+    if not len(values):
+        raise ZeroDivisionError('division by zero')
+    return math.fsum(values) / len(values)

@@ -135,8 +135,9 @@ class RoleExtractor:
         :param measures: node x measure table, e.g. ``graphrole_amd.node_measures(G)`` (with
           ``'betweenness_centrality'``, ``'closeness_centrality'``, ``'harmonic_centrality'``,
           ``'biconnected_components'``, ``'core_number'``, ``'onion_layer'``, ``'eccentricity'`` or ``'constraint'``
-          named, or ``graphrole_amd.betweenness_centrality(G)`` or ``graphrole_amd.effective_size(G, weight='weight')``
-          added as a column), a
+          named, ``clustering_weight='weight'`` for the weighted clustering column, or
+          ``graphrole_amd.betweenness_centrality(G)``, ``graphrole_amd.effective_size(G, weight='weight')`` or
+          ``graphrole_amd.clustering(G, weight='weight')`` -- the way in for a directed graph -- added as a column), a
           user-computed column, or the feature table itself; rows are matched to ``node_role_factor.index`` by label (any
           order, the same label set).  Every entry must be a finite number: fill gaps first, e.g.
           ``sense_making(measures.fillna(0))``

@@ -33,8 +33,9 @@ extern "C" {
 #endif
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
-                                    grx_eccentricity, grx_structural_holes, grx_weighted_distances and
-                                    grx_weighted_betweenness joined later under the same number (added entry points only)
+                                    grx_eccentricity, grx_structural_holes, grx_weighted_distances,
+                                    grx_weighted_betweenness and grx_clustering joined later under the same number (added
+                                    entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1084,6 +1085,48 @@ int grx_structural_holes(int64_t n, const int64_t *d_row_ptr, const int32_t *d_c
                          const int64_t *d_out_row_ptr,
                          double *d_constraint, double *d_effective_size, double *d_local,
                          void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_clustering: the clustering coefficient of every node in its weighted and its directed forms --
+ *   networkx.clustering(G, weight=...) of an undirected graph with weights (Onnela: the geometric mean of the three
+ *   normalised weights of each triangle), of a directed graph (Fagiolo) and of a directed graph with weights
+ *   (networkx/algorithms/cluster.py).  With a value s per arc of the CSR
+ *     undirected  s(u, v) = cbrt(w(u, v) / max_weight)
+ *     directed    s(u, v) = cbrt(w(u -> v) / max_weight) + cbrt(w(v -> u) / max_weight), an absent direction adds 0
+ *     t(u) = sum_v s(u, v) * sum_w s(u, w) * s(v, w)          clustering(u) = t == 0 ? 0 : t / denominator(u)
+ *   v over the entries of row u other than u, w over the common entries of rows u and v other than u and v, and
+ *     undirected  denominator = d (d - 1),               d = the entries of row u other than u
+ *     directed    denominator = 2 (dt (dt - 1) - 2 db),  dt = the directions present at those entries, db = dt - d
+ *   (undirected: t is twice networkx's weighted_triangles; directed: its directed_triangles).
+ *   d_row_ptr / d_col: a CSR that is SYMMETRIC in structure (entry (u, v) iff entry (v, u)): row u lists every
+ *   neighbour of u in EITHER direction; columns ascending and distinct inside a row; a diagonal entry is allowed and
+ *   counts neither as a neighbour nor in a triangle.  Rows in any order.  Rows longer than GRX_HUB_FACTOR *
+ *   lanes_per_row (4, 8, 16 or 32) must be listed in d_hub_rows.
+ *   d_fwd: fp64[nnz], at arc (u, v) the weight of u -> v; d_bwd: fp64[nnz], at arc (u, v) the weight of v -> u (so
+ *   d_bwd at (u, v) equals d_fwd at (v, u)).  A NEGATIVE value marks a direction that is absent; at least one of the
+ *   two is present at every arc; a present weight is finite and in [0, max_weight].  A weight of 0 is a present
+ *   direction: it counts in dt and d and contributes 0 to t.
+ *   d_bwd == NULL: an undirected graph, d_fwd symmetric and >= 0 everywhere.
+ *   d_fwd == NULL (d_bwd must be NULL too): an undirected graph without weights; every s is 1, no value array is read
+ *   and max_weight is ignored: the result has the bits of grx_local_structure_measures' clustering.  A directed graph
+ *   without weights passes 1 for a present direction and max_weight = 1.
+ *   max_weight: networkx's max over every edge, self-loops included; finite and > 0 whenever d_fwd is given.  A
+ *   quotient w / max_weight that equals 1 has the cube root 1 without a call of cbrt: constant weights give the bits
+ *   of the form without weights, and there every quantity is an integer, so the result is networkx's bit for bit.
+ *   d_clustering: fp64[n], overwritten.  d_triangles: fp64[n] or NULL, t(u).
+ *   Method: see the header of csrc/grx_clustering.hip: s and the denominator per row, then one lane group per ARC that
+ *   walks the shorter of the two rows and binary-searches the longer one, then a per-row sum of the arc terms.  Bound:
+ *   the sum over arcs of min(d_u, d_v) * ceil(log2 max(d_u, d_v)) dependent 4-byte gathers plus one 8-byte gather per
+ *   common neighbour; one cbrt per arc and direction, none inside the intersection.  Every quotient and product is its
+ *   own IEEE operation; sums are lane-strided with a fixed butterfly.  No floating-point atomics: every output has
+ *   the same bits in every run.
+ *   n < 2^31.  d_workspace: grx_clustering_workspace_bytes(n, nnz) bytes (8 n + 20 nnz), nnz = row_ptr[n]; the call
+ *   reads row_ptr[n] back to check it and so waits for the stream once, before its first launch.
+ */
+size_t grx_clustering_workspace_bytes(int64_t n, int64_t nnz);
+int grx_clustering(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_fwd, const double *d_bwd,
+                   double max_weight, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                   double *d_clustering, double *d_triangles, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
