@@ -17,7 +17,8 @@
 // a graph without weights every quantity is a small integer in fp64: the quotient t / denominator is networkx's own.
 //
 // Three stages, each a launch for the hub rows (one workgroup per row longer than GRX_HUB_FACTOR * L) and one for the
-// rest (a group of L lanes per row), as in grx_structural_holes.hip:
+// rest (a group of L lanes per row); the skeletons are grx_rowjoin.h's, shared with grx_structural_holes.hip, and this
+// file holds what a row accumulates, what a hit contributes and what is written:
 //   (a) per row: s of every arc, the row of every arc, and the denominator from the counted directions;
 //   (b) per arc (u, v), u != v: a group of L lanes walks the shorter of the two rows, lane k entries k, k + L, ...,
 //       and looks every entry up in the longer row by binary search (columns ascend); a hit w outside {u, v} adds
@@ -34,57 +35,11 @@
 // its own IEEE operation, so tests/clustering_oracle.py can form the same terms.
 #pragma clang fp contract(off)
 
-#include "grx_common.h"
+#include "grx_rowjoin.h"
 
 #include <cmath>
-#include <type_traits>
 
 namespace {
-
-constexpr int CL_BLOCK = 256;
-constexpr int CL_ROW_MAX_WG = 2048;      // workgroups of the row kernels (a) and (c)
-constexpr int CL_ARC_MAX_WG = 8192;      // workgroups of the per-arc kernel (b)
-
-struct ClWs {
-    double *s, *term, *den;
-    int32_t *arc_row;
-};
-
-size_t cl_ws_bytes(int64_t n, int64_t nnz)
-{
-    const size_t vec = grx_align_up((size_t)(n > 0 ? n : 1) * 8, 256);
-    const size_t arc = grx_align_up((size_t)(nnz > 0 ? nnz : 1) * 8, 256);
-    return vec + 2 * arc + grx_align_up((size_t)(nnz > 0 ? nnz : 1) * 4, 256);
-}
-
-ClWs cl_carve(void *base, int64_t n, int64_t nnz)
-{
-    char *p = reinterpret_cast<char *>(base);
-    const size_t vec = grx_align_up((size_t)(n > 0 ? n : 1) * 8, 256);
-    const size_t arc = grx_align_up((size_t)(nnz > 0 ? nnz : 1) * 8, 256);
-    ClWs w;
-    w.den = reinterpret_cast<double *>(p); p += vec;
-    w.s = reinterpret_cast<double *>(p); p += arc;
-    w.term = reinterpret_cast<double *>(p); p += arc;
-    w.arc_row = reinterpret_cast<int32_t *>(p);
-    return w;
-}
-
-// fixed-tree workgroup sum (every thread passes its value; the result is valid in thread 0)
-__device__ __forceinline__ double block_sum(double v, double *sm)
-{
-    const int t = threadIdx.x;
-    sm[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = CL_BLOCK / 2; s > 0; s >>= 1) {
-        if (t < s) sm[t] = sm[t] + sm[t + s];
-        __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
-}
 
 // cbrt(w / max_weight); a quotient of exactly 1 needs no call
 __device__ __forceinline__ double cl_root(double w, double max_weight)
@@ -109,222 +64,87 @@ __device__ __forceinline__ double cl_arc_value(const double *__restrict__ fwd, c
     return sf + sb;
 }
 
-// d (d - 1) resp. 2 (dt (dt - 1) - 2 db) from the exact counts d = off-diagonal entries, dt = their directions
-__device__ __forceinline__ double cl_denominator(bool directed, double d, double dt)
-{
-    const int64_t di = (int64_t)d, dti = (int64_t)dt;
-    return directed ? (double)(2 * (dti * (dti - 1) - 2 * (dti - di))) : (double)(di * (di - 1));
-}
-
-// ---- (a) per row --------------------------------------------------------------------------------------------------
-// fwd == NULL: no value array is read and s is not written (every s is 1)
-__global__ __launch_bounds__(CL_BLOCK) void cl_rows_hub_kernel(const int64_t *__restrict__ row_ptr,
-                                                               const int32_t *__restrict__ col,
-                                                               const double *__restrict__ fwd,
-                                                               const double *__restrict__ bwd, double max_weight,
-                                                               const int32_t *__restrict__ hub_rows,
-                                                               double *__restrict__ s, double *__restrict__ den,
-                                                               int32_t *__restrict__ arc_row)
-{
-    __shared__ double sm[CL_BLOCK];
-    const int32_t u = hub_rows[blockIdx.x];
-    const int64_t b = row_ptr[u], e = row_ptr[u + 1];
-    double d = 0.0, dt = 0.0;
-    for (int64_t j = b + threadIdx.x; j < e; j += CL_BLOCK) {
-        arc_row[j] = u;
+// (a) fwd == NULL: no value array is read and s is not written (every s is 1)
+struct cl_rows {
+    const int32_t *__restrict__ col;
+    const double *__restrict__ fwd, *__restrict__ bwd;
+    double max_weight;
+    double *__restrict__ s, *__restrict__ den;
+    int32_t *__restrict__ arc_row;
+    struct Acc { double d, dt; };                            // off-diagonal entries, their directions
+    __device__ __forceinline__ void entry(int64_t u, int64_t j, Acc &a) const
+    {
+        arc_row[j] = (int32_t)u;
         double dirs = 1.0;
         if (fwd) s[j] = cl_arc_value(fwd, bwd, j, max_weight, &dirs);
-        if (col[j] != u) { d += 1.0; dt += dirs; }
+        if (col[j] != (int32_t)u) { a.d += 1.0; a.dt += dirs; }
     }
-    d = block_sum(d, sm);
-    dt = block_sum(dt, sm);
-    if (threadIdx.x == 0) den[u] = cl_denominator(bwd != nullptr, d, dt);
-}
-
-template <int L>
-__global__ __launch_bounds__(CL_BLOCK) void cl_rows_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
-                                                           const int32_t *__restrict__ col,
-                                                           const double *__restrict__ fwd,
-                                                           const double *__restrict__ bwd, double max_weight,
-                                                           int64_t hub_degree, double *__restrict__ s,
-                                                           double *__restrict__ den, int32_t *__restrict__ arc_row)
-{
-    constexpr int RPG = CL_BLOCK / L;                       // rows per workgroup pass
-    const int lane = threadIdx.x % L, slot = threadIdx.x / L;
-    const int64_t groups = (n + RPG - 1) / RPG;
-    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
-        const int64_t u = g * RPG + slot;
-        int64_t b = 0, e = 0;
-        if (u < n) { b = row_ptr[u]; e = row_ptr[u + 1]; }
-        const bool hub = e - b > hub_degree;                // cl_rows_hub_kernel's
-        double d = 0.0, dt = 0.0;
-        if (!hub) {
-            for (int64_t j = b + lane; j < e; j += L) {
-                arc_row[j] = (int32_t)u;
-                double dirs = 1.0;
-                if (fwd) s[j] = cl_arc_value(fwd, bwd, j, max_weight, &dirs);
-                if (col[j] != (int32_t)u) { d += 1.0; dt += dirs; }
-            }
-        }
-        d = grx_group_sum<L>(d);
-        dt = grx_group_sum<L>(dt);
-        if (lane == 0 && u < n && !hub) den[u] = cl_denominator(bwd != nullptr, d, dt);
+    template <class R>
+    __device__ __forceinline__ void reduce(Acc &a, R r) const { a.d = r.sum(a.d); a.dt = r.sum(a.dt); }
+    // d (d - 1) resp. 2 (dt (dt - 1) - 2 db) from the exact counts
+    __device__ __forceinline__ void finish(int64_t u, int64_t, int64_t, const Acc &a) const
+    {
+        const int64_t di = (int64_t)a.d, dti = (int64_t)a.dt;
+        den[u] = bwd ? (double)(2 * (dti * (dti - 1) - 2 * (dti - di))) : (double)(di * (di - 1));
     }
-}
+};
 
-// ---- (b) per arc --------------------------------------------------------------------------------------------------
-// s == NULL: every s is 1
-template <int L>
-__global__ __launch_bounds__(CL_BLOCK) void cl_arc_kernel(int64_t nnz, const int64_t *__restrict__ row_ptr,
-                                                          const int32_t *__restrict__ col,
-                                                          const double *__restrict__ s,
-                                                          const int32_t *__restrict__ arc_row,
-                                                          double *__restrict__ term)
-{
-    constexpr int APG = CL_BLOCK / L;                       // arcs per workgroup pass
-    const int lane = threadIdx.x % L, slot = threadIdx.x / L;
-    const int64_t groups = (nnz + APG - 1) / APG;
-    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
-        const int64_t j = g * APG + slot;
-        double a = 0.0;
-        if (j < nnz) {
-            const int32_t u = arc_row[j], v = col[j];
-            if (u != v) {
-                const int64_t bu = row_ptr[u], eu = row_ptr[u + 1], bv = row_ptr[v], ev = row_ptr[v + 1];
-                const bool walk_u = eu - bu <= ev - bv;     // walk the shorter row, search the longer one
-                const int64_t wb = walk_u ? bu : bv, we = walk_u ? eu : ev;
-                const int64_t sb = walk_u ? bv : bu, se = walk_u ? ev : eu;
-                for (int64_t k = wb + lane; k < we; k += L) {
-                    const int32_t w = col[k];
-                    int64_t lo = sb, hi = se;
-                    while (lo < hi) {
-                        const int64_t mid = lo + (hi - lo) / 2;
-                        if (col[mid] < w) lo = mid + 1; else hi = mid;
-                    }
-                    // u and v are tested at the hit: skipping their two searches up front splits the group before
-                    // the search loop and measured 6 % slower (profiles/clustering.txt)
-                    if (lo < se && col[lo] == w && w != u && w != v) a += s ? s[k] * s[lo] : 1.0;
-                }
-            }
-        }
-        a = grx_group_sum<L>(a);
-        if (lane == 0 && j < nnz) term[j] = s ? s[j] * a : a;
+// (b) s == NULL: every s is 1
+struct cl_arc {
+    const double *__restrict__ s;
+    double *__restrict__ term;
+    struct Acc { double a; };
+    __device__ __forceinline__ bool begin(int32_t u, int32_t v, Acc &) const { return u != v; }
+    // u and v are tested at the hit: skipping their two searches up front splits the group before the search loop and
+    // measured 6 % slower (profiles/clustering.txt)
+    __device__ __forceinline__ void hit(int32_t u, int32_t v, int32_t w, int64_t k, int64_t lo, bool, Acc &a) const
+    {
+        if (w != u && w != v) a.a += s ? s[k] * s[lo] : 1.0;
     }
-}
+    template <class R>
+    __device__ __forceinline__ void reduce(Acc &a, R r) const { a.a = r.sum(a.a); }
+    __device__ __forceinline__ void finish(int64_t j, const Acc &a) const { term[j] = s ? s[j] * a.a : a.a; }
+};
 
-// ---- (c) per row --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cl_emit(int64_t u, double t, const double *__restrict__ den,
-                                        double *__restrict__ clustering, double *__restrict__ triangles)
-{
-    if (triangles) triangles[u] = t;
-    clustering[u] = t == 0.0 ? 0.0 : t / den[u];
-}
-
-__global__ __launch_bounds__(CL_BLOCK) void cl_reduce_hub_kernel(const int64_t *__restrict__ row_ptr,
-                                                                 const int32_t *__restrict__ hub_rows,
-                                                                 const double *__restrict__ term,
-                                                                 const double *__restrict__ den,
-                                                                 double *__restrict__ clustering,
-                                                                 double *__restrict__ triangles)
-{
-    __shared__ double sm[CL_BLOCK];
-    const int32_t u = hub_rows[blockIdx.x];
-    const int64_t b = row_ptr[u], e = row_ptr[u + 1];
-    double t = 0.0;
-    for (int64_t j = b + threadIdx.x; j < e; j += CL_BLOCK) t += term[j];
-    t = block_sum(t, sm);
-    if (threadIdx.x == 0) cl_emit(u, t, den, clustering, triangles);
-}
-
-template <int L>
-__global__ __launch_bounds__(CL_BLOCK) void cl_reduce_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
-                                                             int64_t hub_degree, const double *__restrict__ term,
-                                                             const double *__restrict__ den,
-                                                             double *__restrict__ clustering,
-                                                             double *__restrict__ triangles)
-{
-    constexpr int RPG = CL_BLOCK / L;
-    const int lane = threadIdx.x % L, slot = threadIdx.x / L;
-    const int64_t groups = (n + RPG - 1) / RPG;
-    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
-        const int64_t u = g * RPG + slot;
-        int64_t b = 0, e = 0;
-        if (u < n) { b = row_ptr[u]; e = row_ptr[u + 1]; }
-        const bool hub = e - b > hub_degree;                // cl_reduce_hub_kernel's
-        double t = 0.0;
-        if (!hub)
-            for (int64_t j = b + lane; j < e; j += L) t += term[j];
-        t = grx_group_sum<L>(t);
-        if (lane == 0 && u < n && !hub) cl_emit(u, t, den, clustering, triangles);
+// (c)
+struct cl_reduce {
+    const double *__restrict__ term, *__restrict__ den;
+    double *__restrict__ clustering, *__restrict__ triangles;
+    struct Acc { double t; };
+    __device__ __forceinline__ void entry(int64_t, int64_t j, Acc &a) const { a.t += term[j]; }
+    template <class R>
+    __device__ __forceinline__ void reduce(Acc &a, R r) const { a.t = r.sum(a.t); }
+    __device__ __forceinline__ void finish(int64_t u, int64_t, int64_t, const Acc &a) const
+    {
+        if (triangles) triangles[u] = a.t;
+        clustering[u] = a.t == 0.0 ? 0.0 : a.t / den[u];
     }
-}
+};
 
-// f(std::integral_constant<int, L>) for the lane-group width L = lanes_per_row
-template <class F>
-void cl_with_lanes(int lanes_per_row, F f)
-{
-    switch (lanes_per_row) {
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    default: f(std::integral_constant<int, 32>{}); break;
-    }
-}
+constexpr int CL_VECS = 1, CL_ARCS = 2;                      // workspace: den | s, term | arc_row
 
 }  // namespace
 
 extern "C" {
 
-size_t grx_clustering_workspace_bytes(int64_t n, int64_t nnz) { return cl_ws_bytes(n, nnz); }
+size_t grx_clustering_workspace_bytes(int64_t n, int64_t nnz) { return RjWs(nullptr, n, nnz, CL_VECS, CL_ARCS).bytes(); }
 
 int grx_clustering(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_fwd, const double *d_bwd,
                    double max_weight, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
                    double *d_clustering, double *d_triangles, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    GRX_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "grx_clustering: n = %lld out of range [0, 2^31)", (long long)n);
     GRX_REQUIRE(d_clustering, "grx_clustering: d_clustering is NULL");
     GRX_REQUIRE(d_fwd || !d_bwd, "grx_clustering: d_bwd without d_fwd (a directed graph without weights passes 1 for "
                                  "a present direction)");
     GRX_REQUIRE(!d_fwd || (max_weight > 0.0 && std::isfinite(max_weight)),
                 "grx_clustering: max_weight = %g must be finite and > 0", max_weight);
-    if (n == 0) return GRX_OK;
-    GRX_REQUIRE(d_row_ptr && d_col && d_workspace, "grx_clustering: null pointer");
-    GRX_REQUIRE(lanes_per_row == 4 || lanes_per_row == 8 || lanes_per_row == 16 || lanes_per_row == 32,
-                "grx_clustering: lanes_per_row must be 4, 8, 16 or 32 (got %d)", lanes_per_row);
-    GRX_REQUIRE(n_hub_rows >= 0 && n_hub_rows <= n && (n_hub_rows == 0 || d_hub_rows), "grx_clustering: hub list");
-    hipStream_t st = grx_stream(stream);
-    // the number of arcs is the last row pointer: the workspace is carved by it
-    GRX_REQUIRE(workspace_bytes >= cl_ws_bytes(n, 0), "grx_clustering: workspace %zu bytes, need at least %zu",
-                workspace_bytes, cl_ws_bytes(n, 0));
-    int64_t nnz = 0;
-    GRX_CHECK_HIP(hipMemcpyAsync(&nnz, d_row_ptr + n, sizeof(nnz), hipMemcpyDeviceToHost, st));
-    GRX_CHECK_HIP(hipStreamSynchronize(st));
-    GRX_REQUIRE(nnz >= 0, "grx_clustering: row_ptr[n] = %lld", (long long)nnz);
-    GRX_REQUIRE(workspace_bytes >= cl_ws_bytes(n, nnz), "grx_clustering: workspace %zu bytes, need %zu",
-                workspace_bytes, cl_ws_bytes(n, nnz));
-    const ClWs ws = cl_carve(d_workspace, n, nnz);
-    const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
-    const double *s = d_fwd ? ws.s : nullptr;
-
-    if (n_hub_rows)
-        cl_rows_hub_kernel<<<(unsigned)n_hub_rows, CL_BLOCK, 0, st>>>(d_row_ptr, d_col, d_fwd, d_bwd, max_weight,
-                                                                      d_hub_rows, ws.s, ws.den, ws.arc_row);
-    cl_with_lanes(lanes_per_row, [&](auto width) {
-        constexpr int L = decltype(width)::value;
-        const unsigned rgrid = grx_grid(n, CL_BLOCK / L, CL_ROW_MAX_WG);
-        cl_rows_kernel<L><<<rgrid, CL_BLOCK, 0, st>>>(n, d_row_ptr, d_col, d_fwd, d_bwd, max_weight, hub_degree, ws.s,
-                                                      ws.den, ws.arc_row);
-        if (nnz > 0)
-            cl_arc_kernel<L><<<grx_grid(nnz, CL_BLOCK / L, CL_ARC_MAX_WG), CL_BLOCK, 0, st>>>(
-                nnz, d_row_ptr, d_col, s, ws.arc_row, ws.term);
-        cl_reduce_kernel<L><<<rgrid, CL_BLOCK, 0, st>>>(n, d_row_ptr, hub_degree, ws.term, ws.den, d_clustering,
-                                                        d_triangles);
-    });
-    if (n_hub_rows)
-        cl_reduce_hub_kernel<<<(unsigned)n_hub_rows, CL_BLOCK, 0, st>>>(d_row_ptr, d_hub_rows, ws.term, ws.den,
-                                                                        d_clustering, d_triangles);
-    GRX_LAUNCH_CHECK();
-    return GRX_OK;
+    RjCall c{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row};
+    const int rc = rj_prepare("grx_clustering", c, d_workspace, workspace_bytes, CL_VECS, CL_ARCS, stream);
+    if (rc != GRX_OK || n == 0) return rc;
+    const RjWs ws(d_workspace, n, c.nnz, CL_VECS, CL_ARCS);
+    double *den = ws.row(0), *s = ws.per_arc(0), *term = ws.per_arc(1);
+    return rj_run(c, ws.arc_row(), cl_rows{d_col, d_fwd, d_bwd, max_weight, s, den, ws.arc_row()},
+                  cl_arc{d_fwd ? s : nullptr, term}, cl_reduce{term, den, d_clustering, d_triangles}, true);
 }
 
 }  // extern "C"

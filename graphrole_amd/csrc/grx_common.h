@@ -166,3 +166,29 @@ __device__ __forceinline__ double grx_group_sum(double v)
     for (int off = WIDTH / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WIDTH);
     return v;
 }
+
+template <int WIDTH>
+__device__ __forceinline__ double grx_group_max(double v)
+{
+#pragma unroll
+    for (int off = WIDTH / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, WIDTH));
+    return v;
+}
+
+// Fixed-tree sum (MAX: maximum) over a workgroup of BLOCK threads in sm[BLOCK]: every thread passes its value and
+// every thread gets the result; the tree depends only on BLOCK.  All threads of the workgroup must call it.
+template <int BLOCK, bool MAX = false>
+__device__ __forceinline__ double grx_block_reduce(double v, double *sm)
+{
+    const int t = threadIdx.x;
+    sm[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = BLOCK / 2; s > 0; s >>= 1) {
+        if (t < s) sm[t] = MAX ? fmax(sm[t], sm[t + s]) : sm[t] + sm[t + s];
+        __syncthreads();
+    }
+    const double r = sm[0];
+    __syncthreads();
+    return r;
+}

@@ -53,22 +53,6 @@ PowerWs carve(void *base, int64_t n)
     return w;
 }
 
-// fixed-tree workgroup sum (every thread passes its value; the result is valid in thread 0)
-__device__ __forceinline__ double block_sum(double v, double *sm)
-{
-    const int t = threadIdx.x;
-    sm[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = MS_BLOCK / 2; s > 0; s >>= 1) {
-        if (t < s) sm[t] += sm[t + s];
-        __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
-}
-
 // PageRank start (networkx: x = 1/N, dangling = S == 0): x, y = x / S, per-workgroup dangling partials
 __global__ __launch_bounds__(MS_BLOCK) void pr_init_kernel(int64_t n, const double *__restrict__ S, double x0,
                                                            double *__restrict__ x, double *__restrict__ y,
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(MS_BLOCK) void pr_init_kernel(int64_t n, const doub
         y[v] = x0 * si;
         if (s == 0.0) dang += x0;
     }
-    const double d = block_sum(dang, sm);
+    const double d = grx_block_reduce<MS_BLOCK>(dang, sm);
     if (threadIdx.x == 0) part[MS_MAX_WG + blockIdx.x] = d;
     if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl[CT_DONE] = 0; ctrl[CT_ITERS] = 0; }
 }
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(MS_BLOCK) void power_hub_kernel(const int64_t *__re
     double acc = 0.0;
     if (w) for (int64_t j = b + threadIdx.x; j < e; j += MS_BLOCK) acc += src[col[j]] * w[j];
     else   for (int64_t j = b + threadIdx.x; j < e; j += MS_BLOCK) acc += src[col[j]];
-    const double s = block_sum(acc, sm);
+    const double s = grx_block_reduce<MS_BLOCK>(acc, sm);
     if (threadIdx.x == 0) hacc[v] = s;
 }
 
@@ -172,8 +156,8 @@ __global__ __launch_bounds__(MS_BLOCK) void pr_iter_kernel(int64_t n, const int6
             if (si == 0.0) dang += xn;
         }
     }
-    const double e = block_sum(err, sm);
-    const double d = block_sum(dang, sm);
+    const double e = grx_block_reduce<MS_BLOCK>(err, sm);
+    const double d = grx_block_reduce<MS_BLOCK>(dang, sm);
     if (threadIdx.x == 0) { part[blockIdx.x] = e; part[MS_MAX_WG + blockIdx.x] = d; }
 }
 
@@ -202,7 +186,7 @@ __global__ __launch_bounds__(MS_BLOCK) void ev_iter_kernel(int64_t n, const int6
             sq += zv * zv;
         }
     }
-    const double s = block_sum(sq, sm);
+    const double s = grx_block_reduce<MS_BLOCK>(sq, sm);
     if (threadIdx.x == 0) part[2 * MS_MAX_WG + blockIdx.x] = s;
 }
 
@@ -222,7 +206,7 @@ __global__ __launch_bounds__(MS_BLOCK) void ev_normalize_kernel(int64_t n, const
         err += fabs(xn - x_in[v]);
         x_out[v] = xn;
     }
-    const double e = block_sum(err, sm);
+    const double e = grx_block_reduce<MS_BLOCK>(err, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = e;
 }
 
@@ -240,8 +224,8 @@ __global__ __launch_bounds__(MS_BLOCK) void power_finalize_kernel(int mode, int 
         a += pa[i];
         if (mode == FIN_PAGERANK) b += part[MS_MAX_WG + i];
     }
-    const double ta = block_sum(a, sm);
-    const double tb = block_sum(b, sm);
+    const double ta = grx_block_reduce<MS_BLOCK>(a, sm);
+    const double tb = grx_block_reduce<MS_BLOCK>(b, sm);
     if (t != 0) return;
     if (mode == FIN_INIT) { scal[SC_DSUM] = ta; return; }
     if (mode == FIN_NORM) {

@@ -17,12 +17,9 @@ from . import _lib
 
 c_void_p = ctypes.c_void_p
 HUB_FACTOR = 32          # GRX_HUB_FACTOR in csrc/grx_common.h
-SH_BLOCK = 256           # csrc/grx_structural_holes.hip: threads per workgroup,
-SH_ROW_MAX_WG = 2048     # workgroups of its row kernels (256 / lanes rows per workgroup pass)
-SH_ARC_MAX_WG = 8192     # and of its per-arc kernel (256 / lanes arcs per workgroup pass)
-CL_BLOCK = 256           # csrc/grx_clustering.hip: the same three constants
-CL_ROW_MAX_WG = 2048
-CL_ARC_MAX_WG = 8192
+RJ_BLOCK = 256           # csrc/grx_rowjoin.h (grx_structural_holes, grx_clustering): threads per workgroup,
+RJ_ROW_MAX_WG = 2048     # workgroups of its row kernels (256 / lanes rows per workgroup pass)
+RJ_ARC_MAX_WG = 8192     # and of its per-arc kernel (256 / lanes arcs per workgroup pass)
 
 
 def _ptr(t: Optional[torch.Tensor]):

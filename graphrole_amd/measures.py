@@ -1069,15 +1069,54 @@ def _host_arcs(g):
     return rows, np.asarray(g.col, dtype=np.int64), g.w
 
 
-def _structural_hole_refusals(graph, name: str, weighted: bool) -> None:
-    """What constraint and the weighted effective size refuse, read from the host edge arrays: no device work."""
+def _weight_refusals(graph, weighted: bool, parallel_edges: str, bad_weight: str):
+    """What the row-intersection measures refuse, read from the host edge arrays (no device work): parallel edges
+    (NotImplementedError with the caller's `parallel_edges`) and, with `weighted`, a weight that is not finite or is
+    negative (ValueError with the caller's `bad_weight`).  Returns the host weights that were checked, or None."""
     if _has_parallel_edges(graph):
-        raise NotImplementedError(_unavailable('constraint', bool(graph.directed), True))
-    if weighted:
-        w = _host_arcs(graph.to_csr())[2]
-        if w is not None and len(w) and (not np.all(np.isfinite(w)) or np.min(w) < 0):
-            raise ValueError(f'{name}: edge weights must be finite and >= 0 (networkx computes with whatever it is '
-                             f'given; a negative mutual weight has no meaning as a share of attention)')
+        raise NotImplementedError(parallel_edges)
+    w = _host_arcs(graph.to_csr())[2] if weighted else None
+    if w is not None and len(w) and (not np.all(np.isfinite(w)) or np.min(w) < 0):
+        raise ValueError(bad_weight)
+    return w
+
+
+def _structural_hole_refusals(graph, name: str, weighted: bool) -> None:
+    """What constraint and the weighted effective size refuse."""
+    _weight_refusals(graph, weighted, _unavailable('constraint', bool(graph.directed), True),
+                     f'{name}: edge weights must be finite and >= 0 (networkx computes with whatever it is '
+                     f'given; a negative mutual weight has no meaning as a share of attention)')
+
+
+def _symmetric_union(graph, weighted: bool):
+    """The structurally symmetric CSR of networkx's all_neighbors in internal row order, on the host: the union of the
+    m arcs and their reverses.  Returns (row_ptr, col, inverse, vals): entry inverse[i] of the CSR holds arc i as given,
+    entry inverse[m + i] the same arc seen from its head; vals[i] = its weight (1 without `weighted` or weights)."""
+    g = graph.to_csr()
+    src, dst, w = _host_arcs(g)
+    n = g.n
+    inv = np.asarray(graph._device_graph()[0].inv, dtype=np.int64)
+    a, b = inv[np.asarray(src, dtype=np.int64)], inv[np.asarray(dst, dtype=np.int64)]
+    vals = np.ones(len(a)) if (w is None or not weighted) else np.asarray(w, dtype=np.float64)
+    key, inverse = np.unique(np.concatenate([a, b]) * np.int64(max(n, 1)) + np.concatenate([b, a]),
+                             return_inverse=True)
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=row_ptr[1:])
+    return row_ptr, (key % max(n, 1)).astype(np.int32), inverse.ravel(), vals
+
+
+def _series_of(graph, name: str, nodes, existing: bool, column) -> pd.Series:
+    """The float64 Series `name` behind the sorted labels, or behind the sorted members of `nodes`: the column of
+    ``node_measures`` when that `existing` one serves, empty for a graph without nodes, otherwise the device column
+    (internal row order) that column() computes."""
+    rows = _member_rows(graph, nodes)
+    if existing:
+        series = measures_of(graph, [name])[name]
+    elif graph.to_csr().n == 0:
+        series = pd.Series([], index=pd.Index([]), dtype=np.float64, name=name)
+    else:
+        series = graph._frame([name], [column()], [np.dtype('float64')])[name]
+    return series if rows is None else series.iloc[rows]
 
 
 def _mutual_weight_csr(graph, K, weighted: bool):
@@ -1093,20 +1132,11 @@ def _mutual_weight_csr(graph, K, weighted: bool):
         # power of two and cancels exactly in P = z / sum z and M = z / max z, so the out CSR's own weights serve as z
         cache[weighted] = (out, out.w if weighted else None, None)
         return cache[weighted]
-    # directed: the union of the arcs and their reverses in internal row order, the weights of an arc and of its
-    # reverse summed -- a reciprocal pair gets w(u -> v) + w(v -> u) from both ends, a loop counts twice
-    g = graph.to_csr()
-    src, dst, w = _host_arcs(g)
-    n = g.n
-    inv = np.asarray(host.inv, dtype=np.int64)
-    a, b = inv[np.asarray(src, dtype=np.int64)], inv[np.asarray(dst, dtype=np.int64)]
-    vals = np.ones(len(a)) if (w is None or not weighted) else np.asarray(w, dtype=np.float64)
-    key, inverse = np.unique(np.concatenate([a, b]) * np.int64(max(n, 1)) + np.concatenate([b, a]),
-                             return_inverse=True)
-    z = np.bincount(inverse, weights=np.concatenate([vals, vals]), minlength=len(key))
-    row_ptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=row_ptr[1:])
-    csr = K.DeviceCSR(row_ptr, (key % max(n, 1)).astype(np.int32), z)
+    # directed: the weights of an arc and of its reverse summed -- a reciprocal pair gets w(u -> v) + w(v -> u) from both
+    # ends, a loop counts twice
+    row_ptr, col, inverse, vals = _symmetric_union(graph, weighted)
+    z = np.bincount(inverse, weights=np.concatenate([vals, vals]), minlength=len(col))
+    csr = K.DeviceCSR(row_ptr, col, z)
     cache[weighted] = (csr, csr.w, out.row_ptr)
     return cache[weighted]
 
@@ -1136,17 +1166,10 @@ def _structural_hole_series(G, name: str, nodes, weight) -> pd.Series:
     weighted = _weight_flag(name, weight)
     graph = _adapter(G)
     _structural_hole_refusals(graph, name, weighted)
-    rows = _member_rows(graph, nodes)
-    if name == 'effective_size' and not graph.directed and not weighted:
-        # networkx's ego-graph formula n - 2t/n: the existing column, unchanged
-        series = measures_of(graph, ['effective_size'])['effective_size']
-    elif graph.to_csr().n == 0:
-        series = pd.Series([], index=pd.Index([]), dtype=np.float64, name=name)
-    else:
-        K = graph._K()
-        con, es = _structural_holes(graph, K, weighted, name == 'constraint', name == 'effective_size')
-        series = graph._frame([name], [con if name == 'constraint' else es], [np.dtype('float64')])[name]
-    return series if rows is None else series.iloc[rows]
+    # effective size without weights or directions is networkx's ego-graph formula n - 2t/n: the existing column
+    return _series_of(graph, name, nodes, name == 'effective_size' and not graph.directed and not weighted,
+                      lambda: _structural_holes(graph, graph._K(), weighted, name == 'constraint',
+                                                name == 'effective_size')[name == 'effective_size'])
 
 
 def constraint(G, nodes=None, weight=None) -> pd.Series:
@@ -1201,19 +1224,15 @@ def effective_size(G, nodes=None, weight=None) -> pd.Series:
 
 # ------------------------------------------------------------------------------- weighted and directed clustering
 def _clustering_refusals(graph, weighted: bool) -> None:
-    """What clustering refuses, read from the host edge arrays: no device work."""
-    if _has_parallel_edges(graph):
-        raise NotImplementedError(f'networkx does not implement {CATALOGUE["clustering"]} for a multigraph, and parallel '
-                                  f'edges are merged into one arc here; merge the parallel edges first')
-    if weighted:
-        w = _host_arcs(graph.to_csr())[2]
-        if w is not None and len(w):
-            if not np.all(np.isfinite(w)) or np.min(w) < 0:
-                raise ValueError('clustering: edge weights must be finite and >= 0 (the weight of a triangle is the '
-                                 'cube root of the product of its three normalised weights)')
-            if np.max(w) == 0:
-                raise ValueError('clustering: every edge weight is 0, so the weights cannot be divided by their maximum '
-                                 '(networkx raises ZeroDivisionError)')
+    """What clustering refuses."""
+    w = _weight_refusals(graph, weighted,
+                         f'networkx does not implement {CATALOGUE["clustering"]} for a multigraph, and parallel '
+                         f'edges are merged into one arc here; merge the parallel edges first',
+                         'clustering: edge weights must be finite and >= 0 (the weight of a triangle is the '
+                         'cube root of the product of its three normalised weights)')
+    if w is not None and len(w) and np.max(w) == 0:
+        raise ValueError('clustering: every edge weight is 0, so the weights cannot be divided by their maximum '
+                         '(networkx raises ZeroDivisionError)')
 
 
 def _max_weight(graph, weighted: bool) -> float:
@@ -1229,23 +1248,12 @@ def _directional_csr(graph, K, weighted: bool):
     cache = graph.__dict__.setdefault('_directional', {})
     if weighted in cache:
         return cache[weighted]
-    host = graph._device_graph()[0]
-    g = graph.to_csr()
-    src, dst, w = _host_arcs(g)
-    n = g.n
-    inv = np.asarray(host.inv, dtype=np.int64)
-    a, b = inv[np.asarray(src, dtype=np.int64)], inv[np.asarray(dst, dtype=np.int64)]
-    vals = np.ones(len(a)) if (w is None or not weighted) else np.asarray(w, dtype=np.float64)
-    key, inverse = np.unique(np.concatenate([a, b]) * np.int64(max(n, 1)) + np.concatenate([b, a]),
-                             return_inverse=True)
-    inverse = inverse.ravel()
-    fwd = np.full(len(key), -1.0)
-    bwd = np.full(len(key), -1.0)
-    fwd[inverse[:len(a)]] = vals                                # arc (u, v) as given
-    bwd[inverse[len(a):]] = vals                                # and seen from its head
-    row_ptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=row_ptr[1:])
-    csr = K.DeviceCSR(row_ptr, (key % max(n, 1)).astype(np.int32), fwd)
+    row_ptr, col, inverse, vals = _symmetric_union(graph, weighted)
+    fwd = np.full(len(col), -1.0)
+    bwd = np.full(len(col), -1.0)
+    fwd[inverse[:len(vals)]] = vals                             # arc (u, v) as given
+    bwd[inverse[len(vals):]] = vals                             # and seen from its head
+    csr = K.DeviceCSR(row_ptr, col, fwd)
     cache[weighted] = (csr, csr.w, K.to_device(bwd if len(bwd) else np.zeros(1)))
     return cache[weighted]
 
@@ -1295,15 +1303,9 @@ def clustering(G, nodes=None, weight=None) -> pd.Series:
     weighted = _weight_flag('clustering', weight)
     graph = _adapter(G)
     _clustering_refusals(graph, weighted)
-    rows = _member_rows(graph, nodes)
-    if not graph.directed and not weighted:
-        series = measures_of(graph, ['clustering'])['clustering']      # the triangle-count column, unchanged
-    elif graph.to_csr().n == 0:
-        series = pd.Series([], index=pd.Index([]), dtype=np.float64, name='clustering')
-    else:
-        col = _clustering_column(graph, graph._K(), weighted)
-        series = graph._frame(['clustering'], [col], [np.dtype('float64')])['clustering']
-    return series if rows is None else series.iloc[rows]
+    # undirected without weights: the triangle-count column, unchanged
+    return _series_of(graph, 'clustering', nodes, not graph.directed and not weighted,
+                      lambda: _clustering_column(graph, graph._K(), weighted))
 
 
 def average_clustering(G, nodes=None, weight=None, count_zeros: bool = True) -> float:

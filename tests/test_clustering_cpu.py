@@ -461,10 +461,13 @@ def test_header_declaration_matches_the_ctypes_signature():
     assert 'A NEGATIVE value marks a direction that is absent' in header
     assert callable(kernels.clustering)
     source = open(os.path.join(ROOT, 'graphrole_amd', 'csrc', 'grx_clustering.hip')).read()
-    for constant in ('CL_BLOCK', 'CL_ROW_MAX_WG', 'CL_ARC_MAX_WG'):     # the copies the GPU test sizes its graphs by
-        assert int(re.search(r'constexpr int ' + constant + r' = (\d+);', source).group(1)) == getattr(kernels, constant)
+    shared = open(os.path.join(ROOT, 'graphrole_amd', 'csrc', 'grx_rowjoin.h')).read()
+    assert '#include "grx_rowjoin.h"' in source and 'fp contract(off)' in shared.split('#pragma once')[0]
+    for constant in ('RJ_BLOCK', 'RJ_ROW_MAX_WG', 'RJ_ARC_MAX_WG'):     # the copies the GPU test sizes its graphs by
+        assert int(re.search(r'constexpr int ' + constant + r' = (\d+);', shared).group(1)) == getattr(kernels, constant)
     assert '#pragma clang fp contract(off)' in source
     makefile = open(os.path.join(ROOT, 'graphrole_amd', 'csrc', 'Makefile')).read()
+    assert 'grx_rowjoin.h' in re.search(r'%\.o: %\.hip (.*)', makefile).group(1)      # a dependency of every object
     assert 'grx_clustering.hip' in makefile and 'grx_clustering.o: FILEFLAGS := -ffp-contract=off' in makefile
 
 

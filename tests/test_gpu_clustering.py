@@ -15,14 +15,9 @@ import numpy as np
 import pytest
 
 from tests import clustering_oracle as co
+from tests.rowjoin_graphs import WEIGHTS, _ba60000, _digraph, _named_pairs, _pairs_of, _threshold_pairs
 
 pytestmark = pytest.mark.gpu
-
-WEIGHTS = {
-    'unweighted': None,
-    'integer': lambda a, b: 1 + (7 * a + 13 * b) % 5,
-    'float': lambda a, b: 0.1 + ((31 * a + 17 * b) % 97) / 13.0,
-}
 
 
 def _run(row_ptr, col, fwd=None, bwd=None, max_weight=1.0, lanes=None, want_triangles=True):
@@ -44,34 +39,6 @@ def _check(row_ptr, col, fwd=None, bwd=None, max_weight=1.0, lanes=None, what=''
     if fwd is None:
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])      # integers only
     return got
-
-
-def _pairs_of(G):
-    return [(int(u), int(v)) for u, v in G.edges]
-
-
-@functools.lru_cache(maxsize=None)
-def _named_pairs(key):
-    if key == 'n1':
-        return 1, ()
-    if key == 'n1_loop':
-        return 1, ((0, 0),)
-    if key == 'n2':
-        return 2, ((0, 1),)
-    if key == 'n3_path':
-        return 3, ((0, 1), (1, 2))
-    if key == 'n3_triangle':
-        return 3, ((0, 1), (1, 2), (0, 2))
-    graphs = {
-        'path': lambda: nx.path_graph(300),
-        'star1500': lambda: nx.star_graph(1500),               # a hub with no triangle
-        'K70': lambda: nx.complete_graph(70),                   # 68 common neighbours per arc, rows above a wavefront
-        'K40_40': lambda: nx.complete_bipartite_graph(40, 40),  # every intersection empty
-        'wheel1500': lambda: nx.wheel_graph(1500),              # short rows searched against a 1 499-arc hub row
-        'ba2000': lambda: nx.barabasi_albert_graph(2000, 5, seed=7),
-    }
-    G = graphs[key]()
-    return G.number_of_nodes(), tuple(_pairs_of(G))
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,15 +65,6 @@ def test_kernel_against_the_exact_oracle(key, weights):
         assert np.all(got[0] == 1.0) and np.all(got[1] == 69 * 68)
     if key in ('star1500', 'K40_40', 'path', 'n1', 'n1_loop', 'n2', 'n3_path'):
         assert np.all(got[0] == 0.0) and np.all(got[1] == 0.0)
-
-
-def _threshold_pairs(entries):
-    """A centre (row 0) with `entries` neighbours that form a ring with chords: the centre's row has exactly `entries`
-    entries, every other row at most 5, and every arc of the centre has common neighbours."""
-    pairs = [(0, k) for k in range(1, entries + 1)]
-    pairs += [(k, k % entries + 1) for k in range(1, entries + 1)]
-    pairs += [(k, (k + 6) % entries + 1) for k in range(1, entries + 1, 3)]
-    return entries + 1, pairs
 
 
 @pytest.mark.parametrize('weights', list(WEIGHTS))
@@ -142,18 +100,6 @@ def test_self_loops_and_isolated_rows(weights):
         else:
             co.assert_close(x, y, (weights, 'loops'))
     assert b[0][60] == 0.0 and b[0][61] == 0.0 and b[0][62] == 0.0 and np.any(b[0] > 0)
-
-
-def _digraph():
-    D = nx.gnm_random_graph(40, 150, seed=4, directed=True)
-    rng = random.Random(4)
-    D.add_edges_from([(0, 1), (1, 0), (2, 3), (3, 2), (5, 5)])  # reciprocal pairs and a loop
-    D.add_edges_from([(40, 0), (40, 7)])                        # 40: out-arcs only
-    D.add_edges_from([(3, 41), (9, 41)])                        # 41: in-arcs only
-    D.add_node(42)
-    for u, v in D.edges:
-        D[u][v]['weight'] = rng.choice([0.5, 1.0, 2.0, 7.25])
-    return D
 
 
 @pytest.mark.parametrize('weight', [None, 'weight'])
@@ -198,31 +144,17 @@ def test_zero_weights():
     assert t2[1] == t[1] and c2[1] > c[1] > 0                   # the same triangles over a smaller denominator
 
 
-def _ba60000():
-    from graphrole_amd import synth
-    n = 60000
-    src, dst = synth.ba_edges(n, 5, seed=3)
-    rows, cols = np.concatenate([src, dst]), np.concatenate([dst, src])
-    key = np.unique(rows.astype(np.int64) * n + cols)
-    row_ptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key // n, minlength=n), out=row_ptr[1:])
-    col = (key % n).astype(np.int32)
-    lo, hi = np.minimum(key // n, key % n), np.maximum(key // n, key % n)
-    fwd = 0.1 + ((31 * lo + 17 * hi) % 97) / 13.0                # symmetric
-    return n, row_ptr, col, fwd
-
-
 def test_second_trip_of_the_grid_stride_loops():
-    """BA 60 000 / m = 5 against the sparse oracle.  With 32 lanes a workgroup pass takes CL_BLOCK / 32 = 8 rows or
-    arcs, so the row kernels (cap CL_ROW_MAX_WG) and the per-arc kernel (cap CL_ARC_MAX_WG) both wrap; with the CSR's
+    """BA 60 000 / m = 5 against the sparse oracle.  With 32 lanes a workgroup pass takes RJ_BLOCK / 32 = 8 rows or
+    arcs, so the row kernels (cap RJ_ROW_MAX_WG) and the per-arc kernel (cap RJ_ARC_MAX_WG) both wrap; with the CSR's
     own 4 lanes the per-arc kernel wraps."""
     from graphrole_amd import kernels as K
     n, row_ptr, col, fwd = _ba60000()
     nnz = len(col)
     assert int(np.diff(row_ptr).max()) <= co.MAX_ROW
-    assert n > K.CL_ROW_MAX_WG * (K.CL_BLOCK // 32) and nnz > K.CL_ARC_MAX_WG * (K.CL_BLOCK // 32)
+    assert n > K.RJ_ROW_MAX_WG * (K.RJ_BLOCK // 32) and nnz > K.RJ_ARC_MAX_WG * (K.RJ_BLOCK // 32)
     csr = K.DeviceCSR(row_ptr, col)
-    assert nnz > K.CL_ARC_MAX_WG * (K.CL_BLOCK // csr.lanes_per_row) and csr.n_hubs > 0
+    assert nnz > K.RJ_ARC_MAX_WG * (K.RJ_BLOCK // csr.lanes_per_row) and csr.n_hubs > 0
     max_weight = float(fwd.max())
     want = co.sparse(row_ptr, col, fwd, None, max_weight)
     for lanes in (32, None):

@@ -7,7 +7,6 @@ self-loops, isolated rows, the directed symmetrisation with its out-adjacency ro
 trip of the grid-stride loops against the `sparse` restatement; two runs bit-identical.  API parity: graphrole_amd's
 constraint and effective_size against networkx itself.  Tolerances: tests/structural_holes_oracle.py.
 """
-import functools
 import random
 
 import networkx as nx
@@ -15,14 +14,9 @@ import numpy as np
 import pytest
 
 from tests import structural_holes_oracle as so
+from tests.rowjoin_graphs import WEIGHTS, _ba60000, _digraph, _named_pairs, _pairs_of, _threshold_pairs
 
 pytestmark = pytest.mark.gpu
-
-WEIGHTS = {
-    'unweighted': None,
-    'integer': lambda a, b: 1 + (7 * a + 13 * b) % 5,
-    'float': lambda a, b: 0.1 + ((31 * a + 17 * b) % 97) / 13.0,
-}
 
 
 def _run(row_ptr, col, z, out_row_ptr=None, lanes=None, want=(True, True, True)):
@@ -45,34 +39,6 @@ def _check(row_ptr, col, z, out_row_ptr=None, lanes=None, what=''):
     return got
 
 
-def _pairs_of(G):
-    return [(int(u), int(v)) for u, v in G.edges]
-
-
-@functools.lru_cache(maxsize=None)
-def _named_pairs(key):
-    if key == 'n1':
-        return 1, ()
-    if key == 'n1_loop':
-        return 1, ((0, 0),)
-    if key == 'n2':
-        return 2, ((0, 1),)
-    if key == 'n3_path':
-        return 3, ((0, 1), (1, 2))
-    if key == 'n3_triangle':
-        return 3, ((0, 1), (1, 2), (0, 2))
-    graphs = {
-        'path': lambda: nx.path_graph(300),
-        'star1500': lambda: nx.star_graph(1500),               # a hub with no triangle
-        'K70': lambda: nx.complete_graph(70),                   # 68 common neighbours per arc, rows above a wavefront
-        'K40_40': lambda: nx.complete_bipartite_graph(40, 40),  # every intersection empty
-        'wheel1500': lambda: nx.wheel_graph(1500),              # short rows searched against a 1 499-arc hub row
-        'ba2000': lambda: nx.barabasi_albert_graph(2000, 5, seed=7),
-    }
-    G = graphs[key]()
-    return G.number_of_nodes(), tuple(_pairs_of(G))
-
-
 @pytest.mark.parametrize('weights', list(WEIGHTS))
 @pytest.mark.parametrize('key', ['n1', 'n1_loop', 'n2', 'n3_path', 'n3_triangle', 'path', 'star1500', 'K70', 'K40_40',
                                  'wheel1500', 'ba2000'])
@@ -83,15 +49,6 @@ def test_kernel_against_the_exact_oracle(key, weights):
     if key in ('star1500', 'wheel1500'):
         assert K.DeviceCSR(row_ptr, col).n_hubs == 1            # the centre goes through the hub launches
     _check(row_ptr, col, z, what=(key, weights))
-
-
-def _threshold_pairs(entries):
-    """A centre (row 0) with `entries` neighbours that form a ring with chords: the centre's row has exactly `entries`
-    entries, every other row at most 5, and every arc of the centre has common neighbours."""
-    pairs = [(0, k) for k in range(1, entries + 1)]
-    pairs += [(k, k % entries + 1) for k in range(1, entries + 1)]
-    pairs += [(k, (k + 6) % entries + 1) for k in range(1, entries + 1, 3)]
-    return entries + 1, pairs
 
 
 @pytest.mark.parametrize('weights', list(WEIGHTS))
@@ -114,18 +71,6 @@ def test_self_loops_and_isolated_rows(weights):
     row_ptr, col, z = so.csr_from_pairs(63, pairs, WEIGHTS[weights])
     con, es, _ = _check(row_ptr, col, z, what=weights)
     assert np.isnan(con[60]) and np.isnan(es[62]) and not np.isnan(con[61])
-
-
-def _digraph():
-    D = nx.gnm_random_graph(40, 150, seed=4, directed=True)
-    rng = random.Random(4)
-    D.add_edges_from([(0, 1), (1, 0), (2, 3), (3, 2), (5, 5)])  # reciprocal pairs and a loop
-    D.add_edges_from([(40, 0), (40, 7)])                        # 40: out-arcs only
-    D.add_edges_from([(3, 41), (9, 41)])                        # 41: in-arcs only
-    D.add_node(42)
-    for u, v in D.edges:
-        D[u][v]['weight'] = rng.choice([0.5, 1.0, 2.0, 7.25])
-    return D
 
 
 @pytest.mark.parametrize('weight', [None, 'weight'])
@@ -168,25 +113,16 @@ def test_single_outputs_equal_the_joint_call_and_runs_are_bit_identical():
 
 
 def test_second_trip_of_the_grid_stride_loops():
-    """BA 60 000 / m = 5 against the sparse oracle.  With 32 lanes a workgroup pass takes SH_BLOCK / 32 = 8 rows or
-    arcs, so the row kernels (cap SH_ROW_MAX_WG) and the per-arc kernel (cap SH_ARC_MAX_WG) both wrap; with the CSR's
+    """BA 60 000 / m = 5 against the sparse oracle.  With 32 lanes a workgroup pass takes RJ_BLOCK / 32 = 8 rows or
+    arcs, so the row kernels (cap RJ_ROW_MAX_WG) and the per-arc kernel (cap RJ_ARC_MAX_WG) both wrap; with the CSR's
     own 4 lanes the per-arc kernel wraps."""
     from graphrole_amd import kernels as K
-    from graphrole_amd import synth
-    n = 60000
-    src, dst = synth.ba_edges(n, 5, seed=3)
-    rows, cols = np.concatenate([src, dst]), np.concatenate([dst, src])
-    key = np.unique(rows.astype(np.int64) * n + cols)
-    row_ptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key // n, minlength=n), out=row_ptr[1:])
-    col = (key % n).astype(np.int32)
-    lo, hi = np.minimum(key // n, key % n), np.maximum(key // n, key % n)
-    z = 0.1 + ((31 * lo + 17 * hi) % 97) / 13.0                 # symmetric
+    n, row_ptr, col, z = _ba60000()
     nnz = len(col)
     assert int(np.diff(row_ptr).max()) <= so.MAX_ROW
-    assert n > K.SH_ROW_MAX_WG * (K.SH_BLOCK // 32) and nnz > K.SH_ARC_MAX_WG * (K.SH_BLOCK // 32)
+    assert n > K.RJ_ROW_MAX_WG * (K.RJ_BLOCK // 32) and nnz > K.RJ_ARC_MAX_WG * (K.RJ_BLOCK // 32)
     csr = K.DeviceCSR(row_ptr, col)
-    assert nnz > K.SH_ARC_MAX_WG * (K.SH_BLOCK // csr.lanes_per_row) and csr.n_hubs > 0
+    assert nnz > K.RJ_ARC_MAX_WG * (K.RJ_BLOCK // csr.lanes_per_row) and csr.n_hubs > 0
     want = so.sparse(row_ptr, col, z)
     so.assert_close(_run(row_ptr, col, z, lanes=32), want, row_ptr, 'lanes 32')
     so.assert_close(_run(row_ptr, col, z), want, row_ptr, 'own lanes')

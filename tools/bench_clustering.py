@@ -25,6 +25,7 @@ import csv
 import glob
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -77,8 +78,8 @@ def child(case, n, m):
 
 
 def kernel_split(case, n, m):
-    """{kernel: launches and ms per call} of the cl_* / sh_* kernels from a rocprofv3 run of `--child case` (two calls:
-    halved)."""
+    """{body<lanes> or body_hub: launches and ms per call} of the grx_rowjoin.h kernels, by their cl_* / sh_* bodies, from
+    a rocprofv3 run of `--child case` (two calls: halved)."""
     if shutil.which('rocprofv3') is None:
         return {'error': 'rocprofv3 not found'}
     out_dir = tempfile.mkdtemp(prefix='cl_prof_')
@@ -91,11 +92,10 @@ def kernel_split(case, n, m):
         split = {}
         for path in glob.glob(os.path.join(out_dir, '**', '*kernel_stats.csv'), recursive=True):
             for row in csv.DictReader(open(path)):
-                name = row.get('Name', '')
-                tag = next((t for t in ('cl_', 'sh_') if t in name), None)
-                if tag is None:
+                found = re.search(r'(rj_\w+)<(?:(\d+), )?.*?((?:cl|sh)_\w+)>', row.get('Name', ''))
+                if found is None:
                     continue
-                key = name[name.index(tag):].split('(')[0]
+                key = '%s<%s>' % (found.group(3), found.group(2)) if found.group(2) else found.group(3) + '_hub'
                 split[key] = {'calls': int(row['Calls']) // 2, 'ms': round(float(row['TotalDurationNs']) / 2e6, 4)}
         return dict(sorted(split.items(), key=lambda kv: -kv[1]['ms'])) or {'error': 'no kernel_stats.csv rows'}
     finally:
