@@ -275,6 +275,9 @@ _SIGNATURES = {
     'grx_clustering_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'grx_clustering': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int,
                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'grx_square_clustering_workspace_bytes': (c_size_t, [c_int64]),
+    'grx_square_clustering': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -20,6 +20,8 @@ HUB_FACTOR = 32          # GRX_HUB_FACTOR in csrc/grx_common.h
 RJ_BLOCK = 256           # csrc/grx_rowjoin.h (grx_structural_holes, grx_clustering): threads per workgroup,
 RJ_ROW_MAX_WG = 2048     # workgroups of its row kernels (256 / lanes rows per workgroup pass)
 RJ_ARC_MAX_WG = 8192     # and of its per-arc kernel (256 / lanes arcs per workgroup pass)
+SQ_WAVE_MAX_WEDGES = 768     # csrc/grx_square_clustering.hip: rows with at most this many wedges count in a one-wavefront
+SQ_LDS_MAX_WEDGES = 3072     # LDS table, up to this many in a four-wavefront one, above in dense counters in HBM
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1430,3 +1432,21 @@ def clustering(csr: DeviceCSR, fwd: Optional[torch.Tensor] = None, bwd: Optional
     _lib.call('grx_clustering', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(fwd), _ptr(bwd), float(max_weight), hub_ptr,
               n_hubs, lanes_per_row, _ptr(cl), _ptr(tri), _ptr(ws), ws_bytes, _stream())
     return cl, tri
+
+
+def square_clustering(csr: DeviceCSR, want_counts: bool = False,
+                      lanes: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """grx_square_clustering on the symmetric CSR of the distinct arcs of an undirected graph (a diagonal entry is a
+    self-loop; csr.w is not read): (square clustering fp64[n], squares int64[n] -- networkx's numerator, the 4-cycles
+    through the node --, potential int64[n] -- its denominator), the last two None unless want_counts.  lanes = lanes
+    per row of the row-statistics launch (4, 8, 16 or 32; None = csr.lanes_per_row), with the hub list of that
+    width."""
+    n = csr.n
+    ws, ws_bytes = _workspace('grx_square_clustering_workspace_bytes', n)
+    c4 = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    squares = torch.empty(max(n, 1), dtype=torch.int64, device=device()) if want_counts else None
+    potential = torch.empty(max(n, 1), dtype=torch.int64, device=device()) if want_counts else None
+    hub_ptr, n_hubs, lanes_per_row, _keep = _hubs_for(csr, lanes)
+    _lib.call('grx_square_clustering', n, _ptr(csr.row_ptr), _ptr(csr.col), hub_ptr, n_hubs, lanes_per_row, _ptr(c4),
+              _ptr(squares), _ptr(potential), _ptr(ws), ws_bytes, _stream())
+    return c4, squares, potential

@@ -24,7 +24,11 @@ and -- with ``clustering`` / ``average_clustering`` or ``node_measures(..., clus
 clustering coefficient of a directed graph (Fagiolo) and of a graph with weights (Onnela's geometric mean of the
 normalised triangle weights), as networkx's ``clustering(G, nodes, weight)`` defines them, by
 csrc/grx_clustering.hip: the cube root of every normalised weight once per arc, then the per-arc row intersections of
-the structural-hole kernel over the all-neighbours CSR.
+the structural-hole kernel over the all-neighbours CSR, and -- with ``square_clustering`` -- the square clustering
+coefficient of an undirected graph (the density of 4-cycles, the one local density that says anything on a bipartite
+graph), as networkx's ``square_clustering(G, nodes)`` defines it, by csrc/grx_square_clustering.hip: the two-hop
+neighbours of every node counted in an LDS hash table (dense counters for the rows with more than 3 072 wedges), all
+in integers until one division.
 """
 from __future__ import annotations
 
@@ -1298,7 +1302,7 @@ def clustering(G, nodes=None, weight=None) -> pd.Series:
     weights raise (networkx computes with them); weights that are all zero raise ValueError (networkx:
     ZeroDivisionError); a zero result is the float 0.0 (networkx: the int 0); weights so small that networkx's product
     of three normalised weights underflows are outside the comparison.  ``triangles`` of a directed graph,
-    ``transitivity``, ``square_clustering`` and ``generalized_degree`` are not offered.
+    ``transitivity`` and ``generalized_degree`` are not offered; ``square_clustering`` is a function of its own.
     """
     weighted = _weight_flag('clustering', weight)
     graph = _adapter(G)
@@ -1323,3 +1327,52 @@ def average_clustering(G, nodes=None, weight=None, count_zeros: bool = True) -> 
     if not len(values):
         raise ZeroDivisionError('division by zero')
     return math.fsum(values) / len(values)
+
+
+# ------------------------------------------------------------------------------------------------ square clustering
+def square_clustering(G, nodes=None):
+    """
+    The square clustering coefficient of every node on the GPU -- the probability that two neighbours of a node share
+    a common neighbour other than that node (Lind et al. 2005, Zhang et al. 2008): ``nx.square_clustering(G, nodes)``
+    of networkx 3.4.2 (cluster.py).  Triangle clustering is 0 on every bipartite graph; this measure tells a node
+    inside a dense bipartite block (near 1) from a star centre or a tree node (0).  grx_square_clustering
+    (csrc/grx_square_clustering.hip) counts, for every node v, how many neighbours of v each two-hop neighbour x has --
+    row v of A^2 -- in an LDS hash table; networkx's sums over the pairs of neighbours collapse to
+    squares = sum_x C(c(x), 2) and potential = (d - 1) (sum_u k_u - d) - 2 T - squares, T the adjacent pairs among the
+    neighbours, and the value is squares / potential (squares itself when potential <= 0, as networkx leaves it:
+    that is 0 unless self-loops are involved).
+
+    :param G: any undirected graph ``node_measures`` accepts; multigraph edges count once (networkx: ``G[u]`` holds
+      distinct neighbours); self-loops are handled as networkx handles them
+    :param nodes: None = every node; a node = that node only; otherwise the members of the iterable that are nodes
+      (networkx's ``G.nbunch_iter``: others are dropped)
+    :return: float64 Series named ``square_clustering`` indexed by the sorted node labels (the index of
+      ``node_measures``, so ``M['square_clustering'] = square_clustering(G)`` adds the column to a table for
+      ``sense_making``) or by the sorted members of `nodes`; a float for a single node
+    :raises NotImplementedError: a directed graph -- networkx's value there depends on the insertion order of the
+      adjacency (it tests ``w in G[u]`` for one orientation of each pair only), so there is nothing to restate
+
+    Equal to networkx bit for bit while squares and potential are below 2^53: both are exact integers and the quotient
+    is Python's ``int / int``.  Stated divergence: a zero result is the float 0.0 (networkx: the int 0).  The name is
+    not in ``CATALOGUE``: this function is the way in.
+    """
+    graph = _adapter(G)
+    if graph.directed:
+        raise NotImplementedError('square_clustering of a directed graph is not computed here: networkx\'s value there '
+                                  'depends on the insertion order of the adjacency (nx.square_clustering tests '
+                                  '`w in G[u]` for one orientation of each pair of neighbours only)')
+    single = False
+    if nodes is not None:
+        try:
+            single = nodes in set(graph.get_nodes())
+        except TypeError:                                      # unhashable: a container of nodes
+            pass
+    targets = _node_set(graph, nodes)
+    if not targets:                                             # the empty graph, or no member in `nodes`
+        return pd.Series([], index=pd.Index([]), dtype=np.float64, name='square_clustering')
+    column = graph._K().square_clustering(graph._structure_csrs()[0])[0]
+    series = graph._frame(['square_clustering'], [column], [np.dtype('float64')])['square_clustering']
+    if nodes is None:
+        return series
+    series = series.iloc[np.sort(_rows_of(graph, targets))]
+    return float(series.iloc[0]) if single else series

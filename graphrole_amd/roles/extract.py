@@ -137,7 +137,8 @@ class RoleExtractor:
           ``'biconnected_components'``, ``'core_number'``, ``'onion_layer'``, ``'eccentricity'`` or ``'constraint'``
           named, ``clustering_weight='weight'`` for the weighted clustering column, or
           ``graphrole_amd.betweenness_centrality(G)``, ``graphrole_amd.effective_size(G, weight='weight')`` or
-          ``graphrole_amd.clustering(G, weight='weight')`` -- the way in for a directed graph -- added as a column), a
+          ``graphrole_amd.clustering(G, weight='weight')`` -- the way in for a directed graph -- added as a column, or
+          ``M['square_clustering'] = graphrole_amd.square_clustering(G)``, which has no catalogue name), a
           user-computed column, or the feature table itself; rows are matched to ``node_role_factor.index`` by label (any
           order, the same label set).  Every entry must be a finite number: fill gaps first, e.g.
           ``sense_making(measures.fillna(0))``

@@ -34,8 +34,8 @@ extern "C" {
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
                                     grx_eccentricity, grx_structural_holes, grx_weighted_distances,
-                                    grx_weighted_betweenness and grx_clustering joined later under the same number (added
-                                    entry points only)
+                                    grx_weighted_betweenness, grx_clustering and grx_square_clustering joined later under
+                                    the same number (added entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1127,6 +1127,39 @@ size_t grx_clustering_workspace_bytes(int64_t n, int64_t nnz);
 int grx_clustering(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_fwd, const double *d_bwd,
                    double max_weight, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
                    double *d_clustering, double *d_triangles, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_square_clustering: the square clustering coefficient of every node -- networkx.square_clustering(G)
+ *   (networkx/algorithms/cluster.py; Lind et al. 2005, Zhang et al. 2008), the probability that two neighbours of a
+ *   node share a common neighbour other than that node.  With N = the entries of row v (v itself among them when the
+ *   row has a diagonal entry), d = |N| and k_u = the length of row u
+ *     K1   = sum_{u in N} k_u
+ *     c(x) = |{u in N : x in row u}|  for x != v           (row v of A^2, set semantics)
+ *     Q    = sum_{x != v} c(x) (c(x) - 1) / 2              (networkx's numerator: the 4-cycles through v)
+ *     S    = sum_{x in N, x != v} c(x),   L = |{x in N, x != v : row x has a diagonal entry}|
+ *     potential = (d - 1) (K1 - d) - (S - L + (d - 1) [row v has a diagonal entry]) - Q
+ *     square_clustering(v) = potential > 0 ? (double)Q / (double)potential : (double)Q
+ *   which is networkx's sum over the pairs of neighbours, collapsed; every quantity is an integer until the division.
+ *   networkx divides only when potential > 0 and otherwise leaves Q: 0 without self-loops; with them Q > 0 can occur.
+ *   d_row_ptr / d_col: the CSR of the DISTINCT arcs of an undirected graph: SYMMETRIC (entry (u, v) iff entry (v, u));
+ *   columns ascending and distinct inside a row; a diagonal entry is allowed and means a self-loop.  Rows in any order;
+ *   no weights are read.  Rows longer than GRX_HUB_FACTOR * lanes_per_row (4, 8, 16 or 32) must be listed in d_hub_rows.
+ *   d_square_clustering: fp64[n], overwritten.  d_squares: int64[n] or NULL, Q.  d_potential: int64[n] or NULL.
+ *   n < 2^31.  While Q and potential are below 2^53 the quotient is Python's int / int: networkx's value bit for bit.
+ *   Method: see the header of csrc/grx_square_clustering.hip: K1 and the self-loop flag per row, then one workgroup per
+ *   row that counts c(x) over the row's K1 wedges v -> u -> x -- in an open-addressing table in LDS sized from K1
+ *   (rows with K1 <= 3 072; LDS compare-and-swap and add) or in dense int32[n] counters of the workspace that a second
+ *   walk over the wedges cleans (the rows above) -- and forms Q, S, L and the quotient.  Bound: 4 sum_u k_u^2 bytes of
+ *   gathered column ids and one atomic per wedge.  Integer atomics only, whose combined result does not depend on
+ *   their order: every output has the same bits in every run and for every lanes_per_row.
+ *   d_workspace: grx_square_clustering_workspace_bytes(n) bytes = 8 n + 128 * 4 n (K1 and flag per row; 128 sets of dense
+ *   counters, one per workgroup of the dense launch), each array rounded up to 256 bytes.  The call does not wait for
+ *   the stream.
+ */
+size_t grx_square_clustering_workspace_bytes(int64_t n);
+int grx_square_clustering(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                          int64_t n_hub_rows, int lanes_per_row, double *d_square_clustering, int64_t *d_squares,
+                          int64_t *d_potential, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
