@@ -224,6 +224,9 @@ _SIGNATURES = {
                            c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'grx_nmf_fit': (c_int, [c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_double, c_int, c_void_p,
                             c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'grx_nmf_transform_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
+    'grx_nmf_transform': (c_int, [c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_double, c_int, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     'grx_nmf_iterate_rows': (c_int, [c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'grx_packed_row_bytes': (c_int, [c_void_p]),

@@ -38,7 +38,8 @@ const char *const g_prof_names[GRX_K_COUNT] = {
     "nmf_residual_kernel", "add_columns_kernel", "triangle_count_kernel", "egonet_from_triangles_kernel", "lloyd_max (scan+dp+lloyd+assign)",
     "key_bits_kernel", "sel_map_kernel", "sel_hist_kernel", "sel_walk1_kernel", "sel_collect_kernel", "sel_sort_kernel",
     "sel_walk2_kernel", "role_rows_kernel", "sp_round_kernel (+hub)", "sp_finish_kernel (+source)",
-    "wbc relaxation: sp_round_kernel (+hub)", "wb_forward_kernel (+hub)", "wb_backward_kernel (+hub)"};
+    "wbc relaxation: sp_round_kernel (+hub)", "wb_forward_kernel (+hub)", "wb_backward_kernel (+hub)",
+    "transform_norms_kernel", "nmf_transform_block_kernel"};
 }  // namespace
 
 static hipEvent_t prof_get_event()

@@ -13,9 +13,10 @@ Per generation (device kernels in graphrole_amd/csrc, host decisions in features
 """
 from __future__ import annotations
 
+import re
 import time
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -72,6 +73,24 @@ def _has_kernel(agg) -> bool:
     if isinstance(agg, str):
         return agg in _SUPPORTED_AGGS
     return callable(agg) and _KERNEL_FUNCTIONS.get(id(agg)) == getattr(agg, '__name__', None)
+
+
+_AGG_SUFFIX = re.compile(r'^(.*)\(([^()]*)\)$', re.S)
+
+
+def parse_feature_name(name: str, gen0_names) -> Optional[Tuple[str, List[str]]]:
+    """A feature name as ``extract_features()`` spells it -> (generation-0 column, [aggregation of generation 1, ...,
+    aggregation of the last generation]), None when it does not resolve.  ``(agg)`` suffixes are peeled from the right
+    until the rest is a generation-0 name, so an attribute name that itself ends in parentheses resolves as a whole
+    ('attribute_f(x)(sum)' -> ('attribute_f(x)', ['sum']) when 'attribute_f(x)' is a column).  Pure: no device."""
+    rest, chain = str(name), []
+    while rest not in gen0_names:
+        m = _AGG_SUFFIX.match(rest)
+        if m is None:
+            return None
+        rest = m.group(1)
+        chain.append(m.group(2))
+    return rest, chain[::-1]
 
 
 class RecursiveFeatureExtractor:
@@ -198,6 +217,96 @@ class RecursiveFeatureExtractor:
             self._phase_sync()
             self.wall['device_run_s'] = time.perf_counter() - t0
         return self._finalize_features()
+
+    def replay_features(self, columns) -> DataFrameLike:
+        """
+        New (role transfer, Henderson et al. 2012, section 5): exactly the named feature columns on THIS graph --
+        typically ``features.columns`` of the table another graph's ``extract_features()`` returned, so that the two
+        tables can be compared and ``RoleExtractor.transform`` applied.  No pruning: a column of generation g is its
+        aggregation over ``G[node]`` of its generation g - 1 parent, generation 0 comes from the graph.
+
+        :param columns: feature names as ``extract_features()`` spells them: a generation-0 column of this graph
+          followed by zero or more ``(agg)`` suffixes (``parse_feature_name``)
+        :return: DataFrame indexed like ``extract_features()``, columns in the order asked; dtypes are those
+          ``extract_features()`` gives such columns under this extractor's ``aggs``
+
+        Generation by generation, every needed parent aggregated once, through the helpers of the Python-driven
+        generation loop: replaying the columns of this graph's own table returns that table (``DataFrame.equals``,
+        unweighted graphs).  The extractor's stored features are not touched.  The returned frame is registered for
+        the device hand-off like the result of ``extract_features()``.
+        Raises ValueError for names that do not resolve (all of them listed), NotImplementedError for an aggregation
+        without a device kernel and for ``distributed=`` -- before any device work.
+        """
+        columns = [c if isinstance(c, str) else str(c) for c in columns]
+        if self._distributed:
+            raise NotImplementedError('replay_features is not sharded: distributed= is not supported')
+        gen0_names = self.graph.neighborhood_feature_names()
+        parsed = [parse_feature_name(c, gen0_names) for c in columns]
+        unresolved = [c for c, p in zip(columns, parsed) if p is None]
+        if unresolved:
+            raise ValueError(f'replay_features: {len(unresolved)} name(s) are not a generation-0 column of this graph '
+                             f'({gen0_names}) followed by (agg) suffixes: {unresolved}')
+        aggs = self._agg_names()
+        no_kernel = sorted({a for _, chain in parsed for a in chain if a not in _SUPPORTED_AGGS} | set(self._host_callables()))
+        if no_kernel:
+            raise NotImplementedError(f'replay_features: no device kernel for the aggregation(s) {no_kernel} '
+                                      f'(kernel-backed: {list(_SUPPORTED_AGGS)})')
+        if not columns:
+            csr = self.graph.to_csr()
+            return pd.DataFrame(index=csr.label_index() if hasattr(csr, 'label_index') else pd.Index(csr.labels))
+        # the per-generation helpers read and write the working set: give them an empty one and put the stored one back
+        saved = (self._work, self._dtypes, self._i64, self._int32_exact, self.wall)
+        self._work, self._dtypes, self._i64, self._int32_exact, self.wall = OrderedDict(), {}, set(), set(), {}
+        try:
+            return self._replay(columns, parsed, aggs, gen0_names)
+        finally:
+            self._work, self._dtypes, self._i64, self._int32_exact, self.wall = saved
+
+    def _replay(self, columns, parsed, aggs, gen0_names) -> pd.DataFrame:
+        self._shard()
+        K = self._K()
+        n = self._n()
+        names0, cols0, dtypes0 = self.graph.neighborhood_feature_columns()
+        assert list(names0) == list(gen0_names), (names0, gen0_names)
+        # as run_on_device: the integer columns of a run with 'prod' travel as int64 bits
+        if 'prod' in aggs and any(np.dtype(dt).kind in 'iu' for dt in dtypes0):
+            cols0 = [K.convert_f64_to_i64(c) if np.dtype(dt).kind in 'iu' else c for c, dt in zip(cols0, dtypes0)]
+            self._i64 = {nm for nm, dt in zip(names0, dtypes0) if np.dtype(dt).kind in 'iu'}
+        flags = self._int32_flags(names0, dtypes0)
+        self._int32_exact = {nm for nm, ok in zip(names0, flags or []) if ok}
+        for nm, col, dt in zip(names0, cols0, dtypes0):
+            self._work[nm] = col
+            self._dtypes[nm] = dt
+        _, dev_graph, _ = self.graph._device_graph()
+        no_empty_rows = self._no_empty_rows(self.graph._device_graph()[0])
+        f64 = np.dtype('float64')
+        for generation in range(1, max(len(chain) for _, chain in parsed) + 1):
+            # parent -> aggregations wanted of it, both in the order the request first names them
+            wanted: 'OrderedDict[str, List[str]]' = OrderedDict()
+            for base, chain in parsed:
+                if len(chain) >= generation:
+                    parent = base + ''.join(f'({a})' for a in chain[:generation - 1])
+                    asked = wanted.setdefault(parent, [])
+                    if chain[generation - 1] not in asked:
+                        asked.append(chain[generation - 1])
+            prev = list(wanted)
+            f = len(prev)
+            # the extractor's own list first and in its order (the kernels and the summation order of
+            # extract_features()), then what only the request names
+            call_aggs = list(dict.fromkeys(aggs)) + sorted({a for asked in wanted.values() for a in asked} - set(aggs))
+            names = [f'{c}({a})' for a in call_aggs for c in prev]
+            # (call_aggs is the extractor's list unless the request names other aggregations: those join the dtype rule)
+            dtypes = [self._candidate_dtype(self._dtypes.get(c, f64), call_aggs, no_empty_rows) for a in call_aggs for c in prev]
+            if set(call_aggs) <= set(_FAST_AGGS) and not (self._i64 & set(prev)):
+                sub = self._aggregate_fast(K, dev_graph, prev, call_aggs, n, 0, n)
+            else:
+                sub = self._aggregate_general(K, dev_graph, prev, call_aggs, names, dtypes, n, 0, n)
+            for k, a in enumerate(call_aggs):
+                for j, c in enumerate(prev):
+                    if a in wanted[c]:
+                        self._work[names[k * f + j]] = sub[k * f + j]
+                        self._dtypes[names[k * f + j]] = dtypes[k * f + j]
+        return self._frame_of(columns, [self._work[nm] for nm in columns], handoff=True)
 
     def _phase_sync(self) -> None:
         if self.time_phases:

@@ -192,6 +192,22 @@ class DeviceGraphInterface(BaseGraphInterface):
         dt = np.dtype('int64') if host.integral else np.dtype('float64')
         return ['internal_edges', 'external_edges'], [internal, external], [dt, dt]
 
+    def neighborhood_feature_names(self) -> List[str]:
+        """Names of the generation-0 columns in the order of ``neighborhood_feature_columns()`` -- host work only (the
+        name parser of ``RecursiveFeatureExtractor.replay_features`` refuses before anything touches the device)."""
+        names = ['in_degree', 'out_degree', 'total_degree'] if self.to_csr().directed else ['degree']
+        if self._attrs:
+            cached = getattr(self, '_attr_cols', None)
+            if cached is not None:
+                names += cached[0]
+            else:
+                arrays = self._attribute_arrays()
+                if arrays is None:
+                    attr = self._attribute_frame()
+                    arrays = {} if attr is None else dict.fromkeys(attr.columns)
+                names += list(arrays)
+        return names + ['internal_edges', 'external_edges']
+
     def neighborhood_feature_columns(self):
         n1, c1, d1 = self.local_feature_columns()
         n2, c2, d2 = self.egonet_feature_columns()

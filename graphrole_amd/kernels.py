@@ -1143,6 +1143,24 @@ def nmf_fit(X: torch.Tensor, n: int, r: int, omega: np.ndarray, tol: float, max_
     return state, int(info.n_iter)
 
 
+def nmf_transform(X: torch.Tensor, n: int, H: np.ndarray, tol: float = 1e-4, max_iter: int = 200,
+                  out: Optional[torch.Tensor] = None):
+    """grx_nmf_transform: memberships W [r, ld] (device, feature-major like the fit's) of the n rows of the feature-major
+    device table X [F, ld] under the FIXED role x feature factor H (host, r x F) -- sklearn's NMF(solver='mu')
+    .transform.  Returns (W, NmfInfo)."""
+    F = X.shape[0]
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    if H.ndim != 2 or H.shape[1] != F:
+        raise _lib.GrxInvalid(f'H must be [r, F] with F = {F}, got {H.shape}')
+    r = H.shape[0]
+    W = zeros((r, X.shape[1]), dtype=torch.float64) if out is None else out
+    ws, ws_bytes = _workspace('grx_nmf_transform_workspace_bytes', n, F, r)
+    info = _lib.NmfInfo()
+    _lib.call('grx_nmf_transform', n, F, r, _ptr(X), _ld(X), _hptr(H), float(tol), int(max_iter), _ptr(W), _ld(W),
+              ctypes.byref(info), _ptr(ws), ws_bytes, _stream())
+    return W, info
+
+
 # ---------------------------------------------------------------------------------------------- sense making
 def row_counts(csr: DeviceCSR, add_self_loop: bool) -> torch.Tensor:
     """grx_row_sums with the weights ignored: neighbour counts (networkx G.degree() of a weighted graph)."""

@@ -124,6 +124,75 @@ class RoleExtractor:
         self.node_role_factor = pd.DataFrame(node_role, index=features.index, columns=role_labels)
         self.role_feature_factor = pd.DataFrame(role_feature, index=role_labels, columns=features.columns)
 
+    def transform(self, features: pd.DataFrame, tol: float = factor.NMF_TOL, max_iter: int = factor.NMF_MAX_ITER) -> pd.DataFrame:
+        """
+        New (role transfer, Henderson et al. 2012, section 5): the node x role memberships of ANOTHER feature table
+        under the fitted role x feature factor, which stays fixed -- ``model.transform(X)`` of the sklearn
+        ``NMF(solver='mu')`` the reference fits (roles/factor.py:19): W0 = sqrt(X.mean() / r), multiplicative updates
+        of W only, sklearn's stopping rule.
+
+        :param features: node x feature DataFrame whose columns are exactly ``role_feature_factor.columns`` (any order,
+          matched by label), e.g. ``RecursiveFeatureExtractor(G_b).replay_features(features_a.columns)``; non-negative
+          and without NaN, like the table of a fit
+        :return: DataFrame index = ``features.index``, columns role_0 ...; ``.attrs['n_iter']`` holds the iterations run
+
+        H is the CURRENT content of ``role_feature_factor`` (the encoded factor ``extract_role_factors`` stored; the
+        frame is the caller's to edit).  Nothing fitted is changed.  One device call (grx_nmf_transform); a table that
+        ``extract_features()`` / ``replay_features()`` returned unmodified, with its columns in the factor's order, is
+        read from its device copy.
+        """
+        return self._transform(features, tol, max_iter)[0]
+
+    def _transform(self, features: pd.DataFrame, tol: float, max_iter: int):
+        """(the frame ``transform`` returns, its n x r device matrix or None for a table without rows)"""
+        if self.node_role_factor is None or self.role_feature_factor is None:
+            raise ValueError('transform needs fitted roles: call extract_role_factors first')
+        if self.distributed:
+            raise NotImplementedError('transform is not sharded: use an extractor without distributed=')
+        if not isinstance(features, pd.DataFrame):
+            raise ValueError(f'features must be a pandas DataFrame (got {type(features).__name__})')
+        wanted = self.role_feature_factor.columns
+        if features.columns.has_duplicates:
+            raise ValueError('features has duplicate column labels')
+        missing = [c for c in wanted if c not in features.columns]
+        extra = [c for c in features.columns if c not in wanted]
+        if missing or extra:
+            raise ValueError(f'features must have exactly the columns of role_feature_factor: missing {missing}, '
+                             f'unexpected {extra}')
+        if not features.columns.equals(wanted):
+            features = features[list(wanted)]
+        H = np.ascontiguousarray(self.role_feature_factor.to_numpy(dtype=np.float64))
+        if not np.isfinite(H).all() or (H < 0).any():
+            raise ValueError('role_feature_factor must hold finite non-negative numbers')
+        roles = list(self.role_feature_factor.index)
+        from graphrole_amd import backend
+        K = backend.get()
+        Xd, (n, F) = factor.device_matrix(features)
+        if n == 0:
+            frame = pd.DataFrame(np.zeros((0, len(roles))), index=features.index, columns=roles)
+            frame.attrs['n_iter'] = 0
+            return frame, None
+        W, info = K.nmf_transform(Xd, n, H, tol, max_iter)
+        G = K.transpose(W, len(roles), n)                      # n x r row-major, the layout of the result
+        frame = pd.DataFrame(K.to_host(G), index=features.index, columns=roles)
+        frame.attrs['n_iter'] = int(info.n_iter)
+        return frame, G
+
+    def transform_roles(self, features: pd.DataFrame, tol: float = factor.NMF_TOL,
+                        max_iter: int = factor.NMF_MAX_ITER) -> Dict[Node, str]:
+        """New: node -> label of the dominant role of ``transform(features, tol, max_iter)`` (first maximum wins, as
+        ``roles``; the arg-max runs on the device: grx_role_argmax)."""
+        frame, G = self._transform(features, tol, max_iter)
+        if G is None:
+            return {}
+        from graphrole_amd import backend
+        K = backend.get()
+        first = K.to_host(K.role_argmax(G))
+        labels = np.asarray(frame.columns, dtype=object)[np.maximum(first, 0)]
+        if (first < 0).any():
+            labels[first < 0] = np.nan
+        return dict(zip(frame.index.tolist(), labels.tolist()))
+
     def explain(self):
         raise NotImplementedError('Role explanation ("sense making") is not yet implemented.')
 

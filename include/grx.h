@@ -34,8 +34,8 @@ extern "C" {
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
                                     grx_eccentricity, grx_structural_holes, grx_weighted_distances,
-                                    grx_weighted_betweenness, grx_clustering and grx_square_clustering joined later under
-                                    the same number (added entry points only)
+                                    grx_weighted_betweenness, grx_clustering, grx_square_clustering and grx_nmf_transform joined
+                                    later under the same number (added entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -702,6 +702,31 @@ int grx_nmf_mu(int64_t n, int F, int r, const double *d_X, int64_t ldx, double *
 int grx_nmf_fit(int64_t n, int F, int r, const double *d_X, int64_t ldx, const double *h_omega, int n_over,
                 double tol, int max_iter, double *d_W, int64_t ldw, double *d_H, grx_nmf_info *info, grx_comm *comm,
                 const int64_t *h_bounds, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Role transfer: the memberships of the rows of a NEW table under a fitted role x feature factor that stays fixed.
+ * Replaces model.transform(X) of the sklearn NMF(solver='mu') behind graphrole/roles/factor.py:19, i.e.
+ * _fit_transform(X, H=components_, update_H=False) (sklearn/decomposition/_nmf.py) for the Frobenius loss:
+ * W0 = sqrt(X.mean() / r) everywhere, W <- W * (X H^T) / (W H H^T) with zero denominators replaced by float32 eps,
+ * ||X - W H||_F every 10 iterations, stop when (prev - err) / err_init < tol (err_init at W0); a last block shorter
+ * than 10 iterations ends without a check, tol = 0 runs max_iter iterations.
+ *   d_X   feature-major F x ldx device table (non-negative), as the fit reads it;  h_H  r x F row-major on the HOST;
+ *   d_W   r x ldw device output (rows >= n of a column are left alone);  info as for grx_nmf_mu (direct_residuals:
+ *   checks where ||X||^2 - 2<W, X H^T> + <W^T W, H H^T> cancelled -- a relative squared residual <= 1e-8 -- and the
+ *   direct grx_nmf_residual pass ran instead).
+ * X is read twice (sum(X) and ||X||^2 in one pass, X H^T through grx_project) and never inside the loop: a block of up
+ * to ten updates is ONE launch that keeps a row's r values of X H^T and of W in registers and H H^T in LDS.  The error
+ * terms are summed in a fixed order (no floating-point atomics): two calls give the same bits.  The call synchronises
+ * the stream once before the loop and once per checked block, and returns with d_W complete.
+ * Limits as for the fit (1 <= r <= GRX_MAX_ROLES, F <= GRX_MAX_NMF_FEATURES, r + F <= GRX_MAX_NMF_FEATURES above 16
+ * roles: GRX_ERR_UNSUPPORTED); bad arguments are GRX_ERR_INVALID before any HIP call.  n = 0 returns at once; an
+ * all-zero table returns W = 0 with n_iter = max_iter (sklearn's 0 / 0 comparison never stops).  A zero row of X gives a
+ * zero row of W; a zero row of H (a dead role) a zero column of W after the first update.
+ */
+size_t grx_nmf_transform_workspace_bytes(int64_t n, int F, int r);
+int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, const double *h_H, double tol,
+                      int max_iter, double *d_W, int64_t ldw, grx_nmf_info *info, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ RolX encode --------- */
 /*
