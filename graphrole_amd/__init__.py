@@ -17,7 +17,8 @@ def __getattr__(name):
                 'biconnected_component_counts', 'articulation_points', 'biconnected_components', 'core_number',
                 'onion_layers', 'eccentricity', 'diameter', 'radius', 'center', 'periphery', 'constraint',
                 'effective_size', 'dijkstra_path_lengths', 'weighted_betweenness_centrality', 'clustering',
-                'average_clustering', 'square_clustering', 'ConvergenceError'):
+                'average_clustering', 'square_clustering', 'truss_number', 'node_truss_number', 'k_truss',
+                'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     raise AttributeError(name)

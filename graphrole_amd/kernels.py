@@ -1468,3 +1468,21 @@ def square_clustering(csr: DeviceCSR, want_counts: bool = False,
     _lib.call('grx_square_clustering', n, _ptr(csr.row_ptr), _ptr(csr.col), hub_ptr, n_hubs, lanes_per_row, _ptr(c4),
               _ptr(squares), _ptr(potential), _ptr(ws), ws_bytes, _stream())
     return c4, squares, potential
+
+
+def truss_numbers(csr: DeviceCSR, want_node: bool = True,
+                  lanes: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], int, int]:
+    """grx_truss_numbers on the symmetric CSR of the distinct arcs of an undirected graph (no self-loops; csr.w is not
+    read): (arc_truss int32[nnz] = the truss number of the edge at both of its arcs, node_truss int64[n] = the largest
+    at the row, 0 for an empty row, n_rounds, n_levels = the distinct k assigned).  want_node=False passes NULL for
+    node_truss (None then).  lanes = lanes per frontier edge and per row (4, 8, 16 or 32; None = csr.lanes_per_row),
+    with the hub list of that width."""
+    n = csr.n
+    ws, ws_bytes = _workspace('grx_truss_numbers_workspace_bytes', n, csr.nnz)
+    arc = torch.empty(max(csr.nnz, 1), dtype=torch.int32, device=device())
+    node = torch.empty(max(n, 1), dtype=torch.int64, device=device()) if want_node else None
+    n_rounds, n_levels = ctypes.c_int64(0), ctypes.c_int64(0)
+    hub_ptr, n_hubs, lanes_per_row, _keep = _hubs_for(csr, lanes)
+    _lib.call('grx_truss_numbers', n, _ptr(csr.row_ptr), _ptr(csr.col), hub_ptr, n_hubs, lanes_per_row, _ptr(arc),
+              _ptr(node), ctypes.byref(n_rounds), ctypes.byref(n_levels), _ptr(ws), ws_bytes, _stream())
+    return arc, node, int(n_rounds.value), int(n_levels.value)

@@ -28,7 +28,10 @@ the structural-hole kernel over the all-neighbours CSR, and -- with ``square_clu
 coefficient of an undirected graph (the density of 4-cycles, the one local density that says anything on a bipartite
 graph), as networkx's ``square_clustering(G, nodes)`` defines it, by csrc/grx_square_clustering.hip: the two-hop
 neighbours of every node counted in an LDS hash table (dense counters for the rows with more than 3 072 wedges), all
-in integers until one division.
+in integers until one division, and -- with ``truss_number`` / ``node_truss_number`` / ``k_truss`` -- the truss number
+of every edge and node of an undirected graph (the largest k with the edge or node in networkx's ``k_truss(G, k)``), by
+the level-synchronous edge peeling of csrc/grx_truss.hip: a row intersection per edge for the triangle supports and
+one more per edge as the edges leave, all in integers.
 """
 from __future__ import annotations
 
@@ -1376,3 +1379,136 @@ def square_clustering(G, nodes=None):
         return series
     series = series.iloc[np.sort(_rows_of(graph, targets))]
     return float(series.iloc[0]) if single else series
+
+
+# ---------------------------------------------------------------------------------------------------- truss numbers
+def _truss_refusals(graph, what: str) -> None:
+    """networkx's own limits of k_truss: a directed graph, a multigraph (by the adapter's flag or by parallel edges in
+    its edge list) and a self-loop.  Read from the adapter and the host CSR: no device work."""
+    if graph.directed:
+        raise NotImplementedError(f'networkx does not implement nx.k_truss(G, k) for a directed graph; {what} is not '
+                                  f'computed there')
+    multi = bool(getattr(graph, '_multi', False))
+    g = graph.to_csr()
+    if not multi and hasattr(graph, '_is_simple') and not graph._is_simple():
+        multi = graph.get_num_edges() != g.num_edges
+    if multi:
+        raise NotImplementedError(f'networkx does not implement nx.k_truss(G, k) for a multigraph; {what} is not '
+                                  f'computed there')
+    if getattr(g, 'n_loops', 1) > 0:
+        raise NotImplementedError(f'networkx does not implement nx.k_truss(G, k) for a graph with self-loops; remove '
+                                  f'them first: G.remove_edges_from(nx.selfloop_edges(G))')
+
+
+def _on_host(K, array) -> np.ndarray:
+    return array if isinstance(array, np.ndarray) else np.asarray(K.to_host(array))
+
+
+def truss_number(G) -> pd.Series:
+    """
+    The truss number of every edge on the GPU -- the largest k such that the edge belongs to the k-truss, the maximal
+    subgraph in which every edge lies in at least k - 2 triangles of that subgraph (Cohen 2008): the largest k with the
+    edge in ``nx.k_truss(G, k)`` of networkx 3.4.2 (core.py), at least 2.  One call of grx_truss_numbers
+    (csrc/grx_truss.hip) gives every k at once: the triangle support of every edge by one row intersection per edge,
+    then a level-synchronous peeling of the edges (PKT, Kabir and Madduri 2017) in which every triangle is taken away
+    exactly once, also when two of its edges leave in the same round.
+
+    :param G: any undirected graph ``node_measures`` accepts
+    :return: int64 Series named ``truss_number``, one entry per edge, indexed by a two-level MultiIndex (levels ``u``,
+      ``v``) of the edge's node labels with u before v in the order of the ``node_measures`` index (the sorted labels)
+      and the rows in lexicographic order of that; ``.attrs['rounds']`` = the peeling rounds run, ``.attrs['levels']``
+      = the distinct truss numbers assigned.  Equal to networkx (integers)
+    :raises NotImplementedError: G is directed, a multigraph or has a self-loop (remove them with
+      ``G.remove_edges_from(nx.selfloop_edges(G))``): networkx implements k_truss for none of them -- its own limits,
+      not divergences
+
+    The name is not in ``CATALOGUE``: edges are not rows of the node table; ``node_truss_number`` is the node column.
+    """
+    graph = _adapter(G)
+    _truss_refusals(graph, 'truss_number')
+    g = graph.to_csr()
+    if g.n == 0 or g.num_edges == 0:
+        series = pd.Series(np.zeros(0, dtype=np.int64), name='truss_number',
+                           index=pd.MultiIndex.from_arrays([[], []], names=['u', 'v']))
+        series.attrs.update(rounds=0, levels=0)
+        return series
+    K = graph._K()
+    host = graph._device_graph()[0]
+    csr = graph._structure_csrs()[0]
+    arc, _, rounds, levels = K.truss_numbers(csr, want_node=False)
+    row_ptr = np.asarray(_row_ptr_of(K, csr), dtype=np.int64)
+    nnz = int(row_ptr[-1])
+    perm = np.asarray(host.perm, dtype=np.int64)                # internal row -> row of the sorted labels
+    u = perm[np.repeat(np.arange(host.n, dtype=np.int64), np.diff(row_ptr))]
+    v = perm[_on_host(K, csr.col)[:nnz].astype(np.int64)]
+    t = _on_host(K, arc)[:nnz].astype(np.int64)
+    once = np.nonzero(u < v)[0]
+    once = once[np.lexsort((v[once], u[once]))]
+    labels = _label_index(graph)
+    if isinstance(labels, pd.MultiIndex):                       # tuple labels: each level holds the tuples themselves
+        values = np.empty(len(labels), dtype=object)
+        values[:] = list(labels)
+        ends = [values[u[once]], values[v[once]]]
+    else:
+        ends = [labels.take(u[once]), labels.take(v[once])]
+    series = pd.Series(t[once], name='truss_number', index=pd.MultiIndex.from_arrays(ends, names=['u', 'v']))
+    series.attrs.update(rounds=rounds, levels=levels)
+    return series
+
+
+def _row_ptr_of(K, csr) -> np.ndarray:
+    """The row pointers of a device CSR on the host (kernels.DeviceCSR keeps a copy there)."""
+    host = getattr(csr, '_host', None)
+    return _on_host(K, csr.row_ptr) if host is None else host[0]
+
+
+def node_truss_number(G) -> pd.Series:
+    """
+    The truss number of every node on the GPU -- the largest k such that the node belongs to ``nx.k_truss(G, k)``: the
+    largest truss number of an edge at it, and 0 for a node without an edge (networkx drops isolated nodes from every
+    truss, k = 2 included).  From the same kernel call as ``truss_number``.  It tells the member of a cohesive group
+    from a node that is merely well connected: every node of a complete bipartite block K(5, 5) has core number 5, as
+    the nodes of a 6-clique have, but truss number 2 against the clique's 6.
+
+    :param G: any undirected graph ``node_measures`` accepts
+    :return: int64 Series named ``node_truss_number`` indexed by the sorted node labels (the index of
+      ``node_measures``, so ``M['truss_number'] = node_truss_number(G)`` adds the column to a table for
+      ``sense_making``); ``.attrs['rounds']`` and ``.attrs['levels']`` as in ``truss_number``.  Equal to networkx
+    :raises NotImplementedError: as ``truss_number``
+
+    The name is not in ``CATALOGUE``: this function is the way in.
+    """
+    graph = _adapter(G)
+    _truss_refusals(graph, 'node_truss_number')
+    g = graph.to_csr()
+    if g.n == 0 or g.num_edges == 0:
+        index = _label_index(graph) if g.n else pd.Index([])
+        series = pd.Series(np.zeros(g.n, dtype=np.int64), index=index, name='node_truss_number')
+        series.attrs.update(rounds=0, levels=0)
+        return series
+    _, node, rounds, levels = graph._K().truss_numbers(graph._structure_csrs()[0], want_node=True)
+    series = graph._frame(['node_truss_number'], [node], [np.dtype('int64')])['node_truss_number']
+    series.attrs.update(rounds=rounds, levels=levels)
+    return series
+
+
+def k_truss(G, k):
+    """
+    The k-truss of a networkx graph as ``nx.k_truss(G, k)``: the maximal subgraph in which every edge lies in at least
+    k - 2 triangles of the subgraph, built from the device truss numbers -- an edge-subgraph copy of the edges with
+    ``truss_number >= k`` (graph, node and edge attributes copied; nodes without such an edge dropped, as networkx
+    drops them) -- instead of networkx's repeated Python pass over all edges.
+
+    :param G: an undirected ``networkx.Graph`` without parallel edges and self-loops
+    :param k: the order of the truss
+    :return: a new graph of G's class; ``nx.utils.graphs_equal(k_truss(G, k), nx.k_truss(G, k))`` holds
+    :raises TypeError: G is not a networkx graph: there is no graph to copy -- use ``truss_number(G)`` and select the
+      edges with a value >= k
+    :raises NotImplementedError: as ``truss_number``
+    """
+    import networkx as nx
+    if not isinstance(G, nx.Graph):
+        raise TypeError(f'k_truss returns a networkx graph and takes one (got {type(G).__name__}); for another graph '
+                        f'library use truss_number(G) and keep the edges with a value >= k')
+    t = truss_number(G)
+    return G.edge_subgraph(t.index[t.to_numpy() >= k].tolist()).copy()

@@ -34,8 +34,8 @@ extern "C" {
 
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
                                     grx_eccentricity, grx_structural_holes, grx_weighted_distances,
-                                    grx_weighted_betweenness, grx_clustering, grx_square_clustering and grx_nmf_transform joined
-                                    later under the same number (added entry points only)
+                                    grx_weighted_betweenness, grx_clustering, grx_square_clustering, grx_nmf_transform and
+                                    grx_truss_numbers joined later under the same number (added entry points only)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1185,6 +1185,43 @@ size_t grx_square_clustering_workspace_bytes(int64_t n);
 int grx_square_clustering(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                           int64_t n_hub_rows, int lanes_per_row, double *d_square_clustering, int64_t *d_squares,
                           int64_t *d_potential, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_truss_numbers: the truss number of every edge -- the largest k such that the edge belongs to
+ *   networkx.k_truss(G, k) (networkx/algorithms/core.py; Cohen 2008), the maximal subgraph in which every edge lies in
+ *   at least k - 2 triangles of that subgraph; at least 2 -- and of every node -- the largest truss number of an edge
+ *   at it, 0 for a node without an edge (networkx drops isolated nodes from every truss) -- by one level-synchronous
+ *   peeling of the edges (PKT: Kabir and Madduri 2017): sup(e) = the triangles through e; k = 2; the alive edges with
+ *   sup <= k - 2 (supports as at the start of the round) get t = k and leave, and every triangle one of them closes
+ *   with two edges that have not left in an earlier round is taken away exactly once: the support of each of its
+ *   edges that stays drops by one; when no alive edge has sup <= k - 2, k = 2 + the least support of an alive edge.
+ *   d_row_ptr / d_col: the CSR of the distinct arcs of an undirected graph: SYMMETRIC (entry (u, v) iff entry (v, u)),
+ *   columns ascending and distinct inside a row.  Rows in any order; no weights are read.  PRECONDITION: no self-loop
+ *   entry (networkx raises NetworkXNotImplemented for such a graph; the caller refuses it).  Rows longer than
+ *   GRX_HUB_FACTOR * lanes_per_row (4, 8, 16 or 32) must be listed in d_hub_rows (the node column's launch shape; the
+ *   intersections have no hub path: one group of lanes_per_row lanes per edge whatever the rows' lengths).
+ *   d_arc_truss: int32[nnz], overwritten: t of the edge at BOTH of its arcs.
+ *   d_node_truss: int64[n] or NULL.
+ *   n_rounds: HOST int64 or NULL: the number of rounds run.  n_levels: HOST int64 or NULL: the distinct k assigned.
+ *   Method: see the header of csrc/grx_truss.hip.  The supports are one row intersection per edge (the per-arc kernel
+ *   of csrc/grx_rowjoin.h at the arcs with row < column; the position of every arc's reverse by one binary search
+ *   beside it); the next round's edges are collected in a list by the decrement that takes an edge's support from
+ *   above k - 2 to k - 2; all arcs are swept (twice) only when k jumps.  Cost: 2 intersections per edge over the whole
+ *   call, each min(d_u, d_v) * ceil(log2 max(d_u, d_v)) dependent 4-byte gathers; in the peel two more 4-byte gathers
+ *   per common neighbour and at most 3 integer atomic decrements per triangle; 2 sweeps of at most 8 nnz bytes per
+ *   distinct k; 4 launches per round, 16 rounds enqueued per read-back of the control words.
+ *   Exact (integers only; the outputs do not depend on the order of the atomics): the same bits in every run, for
+ *   every lanes_per_row and for every relabelling of the rows.
+ *   n < 2^31 and nnz = row_ptr[n] < 2^31 (per-arc positions are int32), nnz even.  d_workspace:
+ *   grx_truss_numbers_workspace_bytes(n, nnz) bytes (24 nnz: six int32 per arc, each array rounded up to 256 bytes,
+ *   + 256).  n == 0 or nnz == 0: GRX_OK with nothing launched but the zeroing of d_node_truss.  Otherwise the call
+ *   reads row_ptr[n] back to check it and waits for the stream at every read-back of the round loop; the node
+ *   column is enqueued behind the last one and not waited for.
+ */
+size_t grx_truss_numbers_workspace_bytes(int64_t n, int64_t nnz);
+int grx_truss_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                      int64_t n_hub_rows, int lanes_per_row, int32_t *d_arc_truss, int64_t *d_node_truss,
+                      int64_t *n_rounds, int64_t *n_levels, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
