@@ -1486,3 +1486,24 @@ def truss_numbers(csr: DeviceCSR, want_node: bool = True,
     _lib.call('grx_truss_numbers', n, _ptr(csr.row_ptr), _ptr(csr.col), hub_ptr, n_hubs, lanes_per_row, _ptr(arc),
               _ptr(node), ctypes.byref(n_rounds), ctypes.byref(n_levels), _ptr(ws), ws_bytes, _stream())
     return arc, node, int(n_rounds.value), int(n_levels.value)
+
+
+def graphlet_orbits(csr: DeviceCSR, want_noninduced: bool = False, want_arc_triangles: bool = False,
+                    lanes: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """grx_graphlet_orbits on the symmetric CSR of the distinct arcs of an undirected graph (no self-loops; csr.w is not
+    read): (orbits int64[15, n] = the graphlet degree vectors, one contiguous row per orbit, noninduced int64[15, n] =
+    the non-induced counts they are recovered from, arc_triangles int32[nnz] = the triangles through the edge at both
+    of its arcs), the last two None unless asked for.  The 4-cycles through every node come from
+    square_clustering(csr, want_counts=True) and the 4-cliques are listed on csr.oriented().  lanes = lanes per row and
+    per arc (4, 8, 16 or 32; None = csr.lanes_per_row), with the hub list of that width."""
+    n = csr.n
+    squares = square_clustering(csr, want_counts=True, lanes=lanes)[1]
+    o = csr.oriented()
+    ws, ws_bytes = _workspace('grx_graphlet_orbits_workspace_bytes', n, csr.nnz)
+    orbits = torch.empty((15, n), dtype=torch.int64, device=device())
+    non = torch.empty((15, n), dtype=torch.int64, device=device()) if want_noninduced else None
+    tri = torch.empty(max(csr.nnz, 1), dtype=torch.int32, device=device()) if want_arc_triangles else None
+    hub_ptr, n_hubs, lanes_per_row, _keep = _hubs_for(csr, lanes)
+    _lib.call('grx_graphlet_orbits', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(o.row_ptr), _ptr(o.col), hub_ptr, n_hubs,
+              lanes_per_row, _ptr(squares), _ptr(orbits), _ptr(non), _ptr(tri), _ptr(ws), ws_bytes, _stream())
+    return orbits, non, tri

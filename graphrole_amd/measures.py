@@ -31,7 +31,11 @@ neighbours of every node counted in an LDS hash table (dense counters for the ro
 in integers until one division, and -- with ``truss_number`` / ``node_truss_number`` / ``k_truss`` -- the truss number
 of every edge and node of an undirected graph (the largest k with the edge or node in networkx's ``k_truss(G, k)``), by
 the level-synchronous edge peeling of csrc/grx_truss.hip: a row intersection per edge for the triangle supports and
-one more per edge as the edges leave, all in integers.
+one more per edge as the edges leave, all in integers, and -- with ``graphlet_degree_vectors`` / ``graphlet_counts`` --
+the graphlet degree vector of every node of a simple undirected graph (Przulj's orbits 0-14 of the graphs on 2, 3 and 4
+nodes, induced; there is no networkx function to restate: the authority is brute-force enumeration), by
+csrc/grx_graphlets.hip: non-induced counts from degrees, triangles per edge, the 4-cycles of the square-clustering
+kernel and a 4-clique listing on the degree-oriented graph, then an integer back-substitution.
 """
 from __future__ import annotations
 
@@ -1512,3 +1516,100 @@ def k_truss(G, k):
                         f'library use truss_number(G) and keep the edges with a value >= k')
     t = truss_number(G)
     return G.edge_subgraph(t.index[t.to_numpy() >= k].tolist()).copy()
+
+
+# ------------------------------------------------------------------------------------------ graphlet degree vectors
+#: the nine connected graphs on 2, 3 and 4 nodes: name -> (an orbit of the graphlet, how often a copy holds it)
+_GRAPHLETS = {'edge': (0, 2), 'path3': (2, 1), 'triangle': (3, 3), 'path4': (4, 2), 'star4': (7, 1), 'cycle4': (8, 4),
+              'paw': (9, 1), 'diamond': (13, 2), 'clique4': (14, 4)}
+_ORBIT_COLUMNS = [f'orbit_{k}' for k in range(15)]
+
+
+def _graphlet_refusals(graph, what: str) -> None:
+    """Graphlets are defined on a simple undirected graph: a directed graph, a multigraph (by the adapter's flag or by
+    parallel edges in its edge list) and a self-loop are refused, each with its remedy.  Read from the adapter and the
+    host CSR: no device work."""
+    if graph.directed:
+        raise NotImplementedError(f'{what}: graphlet orbits 0-14 are those of an undirected graph; a directed graph is '
+                                  f'not computed here: pass G.to_undirected()')
+    multi = bool(getattr(graph, '_multi', False))
+    g = graph.to_csr()
+    if not multi and hasattr(graph, '_is_simple') and not graph._is_simple():
+        multi = graph.get_num_edges() != g.num_edges
+    if multi:
+        raise NotImplementedError(f'{what}: graphlet orbits count induced subgraphs of a simple graph; a multigraph is '
+                                  f'not computed here: pass nx.Graph(G), which merges the parallel edges')
+    if getattr(g, 'n_loops', 1) > 0:
+        raise NotImplementedError(f'{what}: graphlet orbits count induced subgraphs of a graph without self-loops; '
+                                  f'remove them first: G.remove_edges_from(nx.selfloop_edges(G))')
+
+
+def _graphlet_totals(frame: pd.DataFrame) -> dict:
+    return {name: int(frame[f'orbit_{orbit}'].to_numpy().sum()) // times for name, (orbit, times) in _GRAPHLETS.items()}
+
+
+def graphlet_degree_vectors(G, nodes=None):
+    """
+    The graphlet degree vector of every node on the GPU (Przulj 2007): for each of the 15 automorphism orbits of the
+    connected graphs on 2, 3 and 4 nodes, the number of induced subgraphs that touch the node at that orbit -- the
+    standard signature of a node's local structure, of which ``clustering``, ``square_clustering``, ``truss_number``
+    and the structural-hole measures are scalar summaries.  Orbit 0: an edge (the degree); 1, 2: end and middle of a
+    path on 3; 3: triangle; 4, 5: end and interior of a path on 4; 6, 7: leaf and centre of a claw; 8: 4-cycle; 9, 10,
+    11: the paw's pendant, its triangle nodes off the tail, its triangle node carrying the tail; 12, 13: the diamond's
+    degree-2 and degree-3 (chord) nodes; 14: 4-clique.  It separates a star centre (orbit 7) from the interior of a path
+    (orbit 5), the tail of a paw from its attachment node, the rim of a diamond from its chord, and counts 4-cliques.
+
+    One call of grx_graphlet_orbits (csrc/grx_graphlets.hip): no induced subgraph is enumerated; the non-induced counts
+    come from degrees, triangles per edge, the 4-cycles of grx_square_clustering and a 4-clique listing on the
+    degree-oriented graph, and the orbits follow by integer back-substitution.
+
+    :param G: any undirected graph ``node_measures`` accepts, without parallel edges and self-loops
+    :param nodes: None = every node; a node = that node only; otherwise the members of the iterable that are nodes
+      (as ``square_clustering``)
+    :return: DataFrame of int64 columns ``orbit_0`` ... ``orbit_14`` indexed by the sorted node labels (the index of
+      ``node_measures``, so ``M = M.join(graphlet_degree_vectors(G))`` adds the columns to a table for
+      ``sense_making``) or by the sorted members of `nodes`; a Series (index = the column names) for a single node.
+      ``.attrs['graphlets']`` = the nine induced graphlet totals of the WHOLE graph (``graphlet_counts``) as a dict
+    :raises NotImplementedError: G is directed (pass ``G.to_undirected()``), a multigraph (pass ``nx.Graph(G)``) or has
+      a self-loop (``G.remove_edges_from(nx.selfloop_edges(G))``)
+
+    Exact (integers; equal to brute-force enumeration) while every non-induced count is below 2^53; the same bits in
+    every run and for every relabelling.  No orbit is in ``CATALOGUE``: this function is the way in.
+    """
+    graph = _adapter(G)
+    _graphlet_refusals(graph, 'graphlet_degree_vectors')
+    g = graph.to_csr()
+    if g.n == 0 or g.num_edges == 0:
+        index = _label_index(graph) if g.n else pd.Index([])
+        frame = pd.DataFrame(np.zeros((g.n, 15), dtype=np.int64), index=index, columns=_ORBIT_COLUMNS)
+    else:
+        orbits = graph._K().graphlet_orbits(graph._structure_csrs()[0])[0]
+        frame = graph._frame(_ORBIT_COLUMNS, [orbits[k] for k in range(15)], [np.dtype('int64')] * 15)
+    totals = _graphlet_totals(frame)
+    if nodes is not None:
+        single = False
+        try:
+            single = nodes in set(graph.get_nodes())
+        except TypeError:                                      # unhashable: a container of nodes
+            pass
+        targets = _node_set(graph, nodes)
+        frame = frame.iloc[np.sort(_rows_of(graph, targets))] if targets else frame.iloc[:0]
+        if single:
+            frame = frame.iloc[0]
+    frame.attrs['graphlets'] = totals
+    return frame
+
+
+def graphlet_counts(G) -> pd.Series:
+    """
+    The number of induced copies of each of the nine connected graphs on 2, 3 and 4 nodes in G, from the column sums of
+    ``graphlet_degree_vectors(G)``: the sum of an orbit divided by the number of nodes of a copy that lie on it.
+
+    :param G: as ``graphlet_degree_vectors``
+    :return: int64 Series named ``graphlet_counts`` indexed ``edge, path3, triangle, path4, star4, cycle4, paw,
+      diamond, clique4``
+    :raises NotImplementedError: as ``graphlet_degree_vectors``
+    """
+    totals = graphlet_degree_vectors(G).attrs['graphlets']
+    return pd.Series([totals[name] for name in _GRAPHLETS], index=pd.Index(list(_GRAPHLETS)), dtype=np.int64,
+                     name='graphlet_counts')

@@ -35,7 +35,8 @@ extern "C" {
 #define GRX_VERSION 1100         /* 0.11.0: grx_core_numbers (core number and onion layer of the sense-making measures);
                                     grx_eccentricity, grx_structural_holes, grx_weighted_distances,
                                     grx_weighted_betweenness, grx_clustering, grx_square_clustering, grx_nmf_transform and
-                                    grx_truss_numbers joined later under the same number (added entry points only)
+                                    grx_truss_numbers joined later under the same number (added entry points only);
+                                    so did grx_graphlet_orbits (graphlet degree vectors, orbits 0-14)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1222,6 +1223,50 @@ size_t grx_truss_numbers_workspace_bytes(int64_t n, int64_t nnz);
 int grx_truss_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                       int64_t n_hub_rows, int lanes_per_row, int32_t *d_arc_truss, int64_t *d_node_truss,
                       int64_t *n_rounds, int64_t *n_levels, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_graphlet_orbits: the graphlet degree vector of every node (Przulj 2007): for each of the 15 automorphism orbits
+ *   of the connected graphs on 2, 3 and 4 nodes, the number of INDUCED subgraphs that touch the node at that orbit.
+ *     0 edge | 1, 2 path on 3: end, middle | 3 triangle | 4, 5 path on 4: end, interior | 6, 7 claw: leaf, centre |
+ *     8 4-cycle | 9, 10, 11 paw: pendant, triangle node off the tail, triangle node carrying the tail |
+ *     12, 13 diamond: degree-2 node, degree-3 node (on the chord) | 14 4-clique
+ *   No induced subgraph is enumerated: the non-induced counts N0 .. N14 per node come from d(v), t(e) = the triangles
+ *   through edge e, t(v) = 1/2 sum_u t(vu), S1(v) = sum_u (d(u) - 1), Q(v) = the 4-cycles through v and K4(v) = the
+ *   4-cliques at v (u over the neighbours of v)
+ *     N0 = d   N1 = S1   N2 = C(d, 2)   N3 = t(v)   N4 = sum_u (S1(u) - (d(v) - 1)) - 2 t(v)
+ *     N5 = sum_u ((d(v) - 1)(d(u) - 1) - t(vu))   N6 = sum_u C(d(u) - 1, 2)   N7 = C(d, 3)   N8 = Q(v)
+ *     N9 = sum_u (t(u) - t(uv))   N10 = sum_u t(vu)(d(u) - 2)   N11 = t(v)(d(v) - 2)
+ *     N12 = sum over the triangles {v, u, w} of (t(uw) - 1)   N13 = sum_u C(t(vu), 2)   N14 = K4(v)
+ *   and the orbits follow by back-substitution through a fixed unit upper-triangular integer matrix (N = A o; the table
+ *   is in csrc/grx_graphlets.hip), integer subtraction only.
+ *   d_row_ptr / d_col: the CSR of the distinct arcs of an undirected graph, grx_truss_numbers' contract: SYMMETRIC,
+ *   columns ascending and distinct inside a row, no diagonal entry; n < 2^31, nnz = row_ptr[n] even and < 2^31.  Rows
+ *   longer than GRX_HUB_FACTOR * lanes_per_row (4, 8, 16 or 32) must be listed in d_hub_rows (the row passes' launch
+ *   shape; the intersections have no hub path).
+ *   d_o_row_ptr / d_o_col: an acyclic orientation of the same graph with ascending out-rows, one arc of every edge
+ *   (o_row_ptr[n] = nnz / 2): the degree orientation of grx_orient_count / grx_orient_fill, whose out-rows are bounded
+ *   by sqrt(2 m) whatever the hubs' degrees.
+ *   d_squares: int64[n], Q: d_squares of grx_square_clustering on the same CSR.
+ *   d_orbits: int64[15][n], overwritten, one contiguous column per orbit.  d_noninduced: int64[15][n] or NULL, the N.
+ *   d_arc_triangles: int32[nnz] or NULL, t(e) at BOTH arcs of the edge.
+ *   Method: see the header of csrc/grx_graphlets.hip.  Cost: two row intersections per edge (t(e); the N12 pass only
+ *   for the edges with a triangle), each min(d_u, d_v) * ceil(log2 max(d_u, d_v)) dependent 4-byte gathers, four row
+ *   passes, and the 4-clique listing on the orientation: per oriented triangle min(d+(u), d+(v), d+(w)) * 2 ceil(log2
+ *   max d+) dependent 4-byte gathers, one 64-bit integer atomic per 4-clique found, at most one more per triangle and
+ *   two per arc.
+ *   Exact: integer atomics only and no result depends on their order, so every output has the same bits in every run,
+ *   for every lanes_per_row and for every relabelling of the rows.  The row sums are carried in doubles that hold
+ *   integers: the outputs are exact while every N is below 2^53; the final arithmetic is int64.
+ *   d_workspace: grx_graphlet_orbits_workspace_bytes(n, nnz) bytes (80 n + 12 nnz: ten int64 per node and three int32
+ *   per arc, each array rounded up to 256 bytes).  n == 0: GRX_OK with nothing launched; nnz == 0: the outputs are
+ *   zeroed.  Otherwise the call reads row_ptr[n] and o_row_ptr[n] back to check them and so waits for the stream
+ *   once, before its first launch.
+ */
+size_t grx_graphlet_orbits_workspace_bytes(int64_t n, int64_t nnz);
+int grx_graphlet_orbits(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int64_t *d_o_row_ptr,
+                        const int32_t *d_o_col, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                        const int64_t *d_squares, int64_t *d_orbits, int64_t *d_noninduced, int32_t *d_arc_triangles,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
