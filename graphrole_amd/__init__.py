@@ -18,7 +18,8 @@ def __getattr__(name):
                 'onion_layers', 'eccentricity', 'diameter', 'radius', 'center', 'periphery', 'constraint',
                 'effective_size', 'dijkstra_path_lengths', 'weighted_betweenness_centrality', 'clustering',
                 'average_clustering', 'square_clustering', 'truss_number', 'node_truss_number', 'k_truss',
-                'graphlet_degree_vectors', 'graphlet_counts', 'ConvergenceError'):
+                'graphlet_degree_vectors', 'graphlet_counts', 'neighbor_roles', 'role_mixing_matrix',
+                'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     raise AttributeError(name)

@@ -287,6 +287,8 @@ _SIGNATURES = {
     'grx_graphlet_orbits_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'grx_graphlet_orbits': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'grx_neighbor_roles': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                   c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -994,10 +994,12 @@ def permute_columns(cols: Sequence[torch.Tensor], index: torch.Tensor, n: int) -
     return out[:, :n]
 
 
-def transpose(src: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
-    """[rows, >= cols] row-major (leading dimension src.stride(0)) -> contiguous [cols, rows]."""
-    out = torch.empty((cols, rows), dtype=torch.float64, device=device())
-    _lib.call('grx_transpose', rows, cols, _ptr(src), _ld(src), _ptr(out), rows, _stream())
+def transpose(src: torch.Tensor, rows: int, cols: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[rows, >= cols] row-major (leading dimension src.stride(0)) -> contiguous [cols, rows], or into `out`, a
+    [cols, >= rows] block of contiguous rows (leading dimension out.stride(0))."""
+    if out is None:
+        out = torch.empty((cols, rows), dtype=torch.float64, device=device())
+    _lib.call('grx_transpose', rows, cols, _ptr(src), _ld(src), _ptr(out), _ld(out), _stream())
     return out
 
 
@@ -1507,3 +1509,38 @@ def graphlet_orbits(csr: DeviceCSR, want_noninduced: bool = False, want_arc_tria
     _lib.call('grx_graphlet_orbits', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(o.row_ptr), _ptr(o.col), hub_ptr, n_hubs,
               lanes_per_row, _ptr(squares), _ptr(orbits), _ptr(non), _ptr(tri), _ptr(ws), ws_bytes, _stream())
     return orbits, non, tri
+
+
+NS_LONG_ROW = 1024       # csrc/grx_neighbor_sense.hip: a row with more arcs than this is walked by a whole workgroup
+
+
+def neighbor_lanes(r: int) -> Tuple[int, ...]:
+    """The lanes_per_row values grx_neighbor_roles accepts for r membership columns besides 0 (the library's choice):
+    CL = ceil(r / 2) rounded up to a power of two lanes share a membership row, times 1, 2, 4 or 8 arc slots, at most
+    64."""
+    cl = 1
+    while 2 * cl < r:
+        cl *= 2
+    return tuple(s * cl for s in (1, 2, 4, 8) if s * cl <= 64)
+
+
+def neighbor_roles(csr: DeviceCSR, P: torch.Tensor, mode: str = 'mean', w: Optional[torch.Tensor] = None,
+                   r: Optional[int] = None, lanes: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grx_neighbor_roles: the neighbour-role table N = A P of NeighborSense, FEATURE-major [r, n] (the layout ``gram``
+    reads).  P: fp64 device matrix [n, >= r] row-major (leading dimension P.stride(0)) of the memberships in the row
+    order of `csr`; r: the columns read (None = all of P's).  mode 'sum': N[k, i] = sum over the arcs of row i of
+    w * P[col, k]; 'mean': that sum over the sum of w (0 for a row of zero strength).  w: fp64[nnz] device tensor (None
+    = every arc counts 1; csr.w is NOT read unless passed here).  lanes: 0 or one of neighbor_lanes(r), the same bits
+    for each.  out: an [r, >= n] block of contiguous rows to write into (e.g. the lower half of a [2 r, n] buffer whose upper half
+    holds P^T, so that one Gram pass sees [P | N]); None = a new [r, n] tensor."""
+    if mode not in ('sum', 'mean'):
+        raise ValueError(f"neighbor_roles: mode must be 'sum' or 'mean' (got {mode!r})")
+    n = csr.n
+    r = int(P.shape[1] if r is None else r)
+    assert P.dtype == torch.float64 and P.dim() == 2 and P.shape[0] >= n and P.stride(1) == 1
+    if out is None:
+        out = torch.empty((r, max(n, 1)), dtype=torch.float64, device=device())
+    assert out.dtype == torch.float64 and out.dim() == 2 and out.stride(1) == 1 and (r > 32 or out.shape[0] >= r)
+    _lib.call('grx_neighbor_roles', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(w), _ptr(P), max(P.stride(0), r), r,
+              int(mode == 'mean'), int(lanes), _ptr(out), _ld(out), _stream())
+    return out[:, :n]

@@ -28,7 +28,10 @@ the structural-hole kernel over the all-neighbours CSR, and -- with ``square_clu
 coefficient of an undirected graph (the density of 4-cycles, the one local density that says anything on a bipartite
 graph), as networkx's ``square_clustering(G, nodes)`` defines it, by csrc/grx_square_clustering.hip: the two-hop
 neighbours of every node counted in an LDS hash table (dense counters for the rows with more than 3 072 wedges), all
-in integers until one division, and -- with ``truss_number`` / ``node_truss_number`` / ``k_truss`` -- the truss number
+in integers until one division, and -- with ``neighbor_roles`` / ``role_mixing_matrix``, the tables behind
+``RoleExtractor.neighbor_sense`` (the paper's NeighborSense: each role explained by the roles of its neighbours) -- the
+node x role table N = op(A) P of the memberships of every node's neighbours by csrc/grx_neighbor_sense.hip: a gather
+of one membership row per arc in a summation order fixed by the positions of the row's arcs, and -- with ``truss_number`` / ``node_truss_number`` / ``k_truss`` -- the truss number
 of every edge and node of an undirected graph (the largest k with the edge or node in networkx's ``k_truss(G, k)``), by
 the level-synchronous edge peeling of csrc/grx_truss.hip: a row intersection per edge for the triangle supports and
 one more per edge as the edges leave, all in integers, and -- with ``graphlet_degree_vectors`` / ``graphlet_counts`` --
@@ -1613,3 +1616,167 @@ def graphlet_counts(G) -> pd.Series:
     totals = graphlet_degree_vectors(G).attrs['graphlets']
     return pd.Series([totals[name] for name in _GRAPHLETS], index=pd.Index(list(_GRAPHLETS)), dtype=np.int64,
                      name='graphlet_counts')
+
+
+# ----------------------------------------------------------------------------------------------- NeighborSense
+#: most membership columns of ``neighbor_roles`` (GRX_MAX_ROLES of include/grx.h)
+MAX_ROLES = 32
+
+
+def _neighbor_arguments(what: str, mode: str, direction: str) -> None:
+    if mode not in ('mean', 'sum'):
+        raise ValueError(f"{what}: mode must be 'mean' or 'sum' (got {mode!r})")
+    if direction not in ('out', 'in', 'all'):
+        raise ValueError(f"{what}: direction must be 'out', 'in' or 'all' (got {direction!r})")
+
+
+def _membership_values(graph, memberships, what: str) -> np.ndarray:
+    """The node x role table as float64 rows of the sorted labels, matched by label as ``sense_making`` matches its
+    measures; every refusal of the table is raised here, on the host."""
+    if not isinstance(memberships, pd.DataFrame):
+        raise ValueError(f'{what}: memberships must be a pandas DataFrame (got {type(memberships).__name__})')
+    r = memberships.shape[1]
+    if r < 1 or r > MAX_ROLES:
+        raise ValueError(f'{what}: memberships must have 1 .. {MAX_ROLES} role columns (GRX_MAX_ROLES); got {r}')
+    n = graph.to_csr().n
+    index = _label_index(graph) if n else pd.Index([])
+    if memberships.index.has_duplicates:
+        raise ValueError(f'{what}: memberships has duplicate row labels')
+    if len(memberships.index) != len(index) or not memberships.index.isin(index).all():
+        raise ValueError(f'{what}: memberships must have one row per node of the graph (the same labels)')
+    if not memberships.index.equals(index):
+        memberships = memberships.reindex(index)
+    values = np.empty(memberships.shape, dtype=np.float64)
+    for j, name in enumerate(memberships.columns):
+        column = memberships.iloc[:, j]
+        if not (pd.api.types.is_numeric_dtype(column.dtype) or pd.api.types.is_bool_dtype(column.dtype)):
+            raise ValueError(f'{what}: role {name!r} is not numeric (dtype {column.dtype})')
+        col = column.to_numpy(dtype=np.float64, na_value=np.nan)
+        bad = int(np.count_nonzero(~np.isfinite(col)))
+        if bad:
+            raise ValueError(f'{what}: role {name!r} has {bad} non-finite entries (NaN or inf)')
+        values[:, j] = col
+    return values
+
+
+def _neighbor_refusals(graph, what: str, weighted: bool) -> None:
+    _weight_refusals(graph, weighted,
+                     f'{what}: a multigraph or a graph with parallel edges is not computed here (their weights are '
+                     f'merged into one arc); merge the parallel edges first',
+                     f'{what}: edge weights must be finite and >= 0 (a neighbour share by a negative weight has no '
+                     f'meaning)')
+
+
+def _neighbor_csr(graph, K, weighted: bool, direction: str, what: str):
+    """(device CSR, its weights or None) the neighbour-role pass walks: the out-adjacency, the in-adjacency or -- 'all' on
+    a directed graph -- the symmetric union A + A^T of ``_mutual_weight_csr``.  An undirected graph has one adjacency."""
+    _, out, _ = graph._device_graph()
+    if not graph.directed or direction == 'out':
+        return out, (out.w if weighted else None)
+    if direction == 'in':
+        tr = _weighted_pull(graph, f"{what}(direction='in')")
+        return tr, (tr.w if weighted else None)
+    csr, z, _ = _mutual_weight_csr(graph, K, weighted)
+    return csr, z
+
+
+def _neighbor_stack(graph, values: np.ndarray, weighted: bool, mode: str, direction: str, what: str,
+                    ones: bool = False):
+    """(K, X, host graph): the device block X = [P^T ; N (; 1)] of 2 r (+ 1) feature-major rows of n entries in INTERNAL
+    row order -- P uploaded once, transposed into the upper half (grx_transpose), N = op(A) P written under it by
+    grx_neighbor_roles, and a row of ones when the column sums of N are wanted from the same Gram pass."""
+    K = graph._K()
+    host = graph._device_graph()[0]
+    n, r = values.shape
+    csr, w = _neighbor_csr(graph, K, weighted, direction, what)
+    P = K.to_device(host.to_internal(values))
+    X = K.empty((2 * r + int(ones), n))
+    K.transpose(P, n, r, out=X[:r])
+    K.neighbor_roles(csr, P, mode, w, out=X[r:2 * r])
+    if ones:
+        K.upload_into(X[2 * r], np.ones(n))
+    return K, X, host
+
+
+def neighbor_roles(G, memberships: pd.DataFrame, *, weight=None, mode: str = 'mean',
+                   direction: str = 'out') -> pd.DataFrame:
+    """
+    The neighbour-role table N of RolX NeighborSense (Henderson et al., KDD 2012, section 4) on the GPU: for every node
+    the memberships of its neighbours, N = op(A) P -- summed, or averaged by the weight of the arcs -- the table that
+    ``RoleExtractor.neighbor_sense`` explains by Q >= 0 with P Q ~ N.  One call of grx_neighbor_roles
+    (csrc/grx_neighbor_sense.hip): a gather of one membership row per arc, a fixed summation order per row, the same
+    bits in every run.
+
+    :param G: any graph ``node_measures`` accepts, without parallel edges
+    :param memberships: node x role DataFrame, e.g. ``node_role_factor``, ``role_percentage``, ``transform(features_b)``
+      or one-hot hard roles; rows are matched to the nodes by label (any order, the same label set), entries numeric
+      and finite, 1 .. 32 columns
+    :param weight: None = every arc counts 1; ``'weight'`` = the edge attribute the adapters read
+    :param mode: ``'mean'`` (the weighted average over the neighbours: rows of a row-stochastic P stay stochastic; a
+      node without neighbours or of zero strength gets zeros) or ``'sum'`` (A P itself)
+    :param direction: for a directed graph ``'out'`` = successors (``G[node]``, what ReFeX aggregates over), ``'in'`` =
+      predecessors, ``'all'`` = both, A + A^T: a reciprocal pair's weights add (it counts twice without weights) and so
+      does a self-loop; on an undirected graph all three are the one adjacency, where a self-loop makes the node its own
+      neighbour once, as ``G[u]`` does
+    :return: float64 DataFrame indexed by the sorted node labels (the index of ``node_measures``) with the columns of
+      `memberships`; empty for a graph without nodes
+    :raises ValueError: a bad `mode` / `direction` / `memberships`, a negative or non-finite weight
+    :raises NotImplementedError: a multigraph or parallel edges; another `weight` name; ``direction='in'`` on an adapter
+      without an in-adjacency
+    """
+    what = 'neighbor_roles'
+    _neighbor_arguments(what, mode, direction)
+    weighted = _weight_flag(what, weight)
+    graph = _adapter(G)
+    _neighbor_refusals(graph, what, weighted)
+    values = _membership_values(graph, memberships, what)
+    n, r = values.shape
+    if n == 0:
+        return pd.DataFrame(np.zeros((0, r)), index=pd.Index([]), columns=memberships.columns)
+    K = graph._K()
+    host = graph._device_graph()[0]
+    csr, w = _neighbor_csr(graph, K, weighted, direction, what)
+    N = K.neighbor_roles(csr, K.to_device(host.to_internal(values)), mode, w)
+    table = host.to_label_order(K.to_host(N)).T
+    return pd.DataFrame(np.ascontiguousarray(table), index=_label_index(graph), columns=memberships.columns)
+
+
+def _neighbor_normal_equations(G, memberships: pd.DataFrame, weight, mode: str, direction: str, what: str,
+                               normalize: bool = False):
+    """(K, P^T P, P^T N, the squared column norms of N) from ONE Gram pass over [P | N] on the device; with `normalize`
+    every column of N is divided by its mean over the nodes (a column of mean 0 becomes zeros) -- applied to the normal
+    equations, the column sums coming from the same pass through a row of ones.  K is None for a graph without nodes
+    (all zeros then)."""
+    _neighbor_arguments(what, mode, direction)
+    weighted = _weight_flag(what, weight)
+    graph = _adapter(G)
+    _neighbor_refusals(graph, what, weighted)
+    values = _membership_values(graph, memberships, what)
+    n, r = values.shape
+    if n == 0:
+        return None, np.zeros((r, r)), np.zeros((r, r)), np.zeros(r)
+    K, X, _ = _neighbor_stack(graph, values, weighted, mode, direction, what, ones=normalize)
+    gram = K.gram(X, n)[0]
+    PtP, PtN, nn = gram[:r, :r].copy(), gram[:r, r:2 * r].copy(), np.diag(gram)[r:2 * r].copy()
+    if normalize:
+        means = gram[2 * r, r:2 * r] / n
+        scale = np.where(means != 0, 1.0 / np.where(means != 0, means, 1.0), 0.0)
+        PtN *= scale[None, :]
+        nn *= scale * scale
+    return K, PtP, PtN, nn
+
+
+def role_mixing_matrix(G, memberships: pd.DataFrame, *, weight=None, direction: str = 'out') -> pd.DataFrame:
+    """
+    The role x role table P^T op(A) P: the edge mass between roles, entry (a, b) = the sum over the arcs u -> v of
+    w(u, v) P[u, a] P[v, b].  With one-hot memberships it is the block-model arc count between hard roles; an undirected
+    edge counts from both ends, so a diagonal entry is twice the edges inside a role (a self-loop counts once).  It is
+    the off-diagonal block of the Gram pass of ``RoleExtractor.neighbor_sense`` with ``mode='sum'``: grx_neighbor_roles,
+    then grx_gram over [P | A P].  Sums of small integers are exact.
+
+    :param G, memberships, weight, direction: as ``neighbor_roles``
+    :return: float64 DataFrame, index = the role of the node, columns = the role of its neighbour, both labelled by the
+      columns of `memberships`
+    """
+    _, _, PtN, _ = _neighbor_normal_equations(G, memberships, weight, 'sum', direction, 'role_mixing_matrix')
+    return pd.DataFrame(PtN, index=memberships.columns, columns=memberships.columns)

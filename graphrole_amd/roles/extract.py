@@ -60,6 +60,7 @@ class RoleExtractor:
         self.node_role_factor: Optional[pd.DataFrame] = None
         self.role_feature_factor: Optional[pd.DataFrame] = None
         self.role_measure_factor: Optional[pd.DataFrame] = None
+        self.role_affinity_factor: Optional[pd.DataFrame] = None
         self.model_selection_ = None
 
     @property
@@ -256,6 +257,42 @@ class RoleExtractor:
             E = K.nnls(GtG, GtM, mm)
         self.role_measure_factor = pd.DataFrame(E, index=self.node_role_factor.columns, columns=measures.columns)
         return self.role_measure_factor
+
+    def neighbor_sense(self, G, memberships: Optional[pd.DataFrame] = None, *, weight=None, mode: str = 'mean',
+                       direction: str = 'out', normalize: bool = False) -> pd.DataFrame:
+        """
+        New (RolX NeighborSense, Henderson et al., KDD 2012, section 4): the non-negative role x role table Q with
+        P Q ~ N, column by column min ||P q - n|| over q >= 0, where P holds the memberships and
+        N = ``graphrole_amd.neighbor_roles(G, P, ...)`` the memberships of every node's neighbours.  Row a of Q tells
+        which roles the neighbours of a role-a node have: do hubs attach to hubs or to the periphery, which role
+        bridges which others.  For one-hot memberships with no empty role and ``mode='mean'`` Q is the row-stochastic
+        role-to-role neighbour share.
+
+        :param G: the graph the memberships belong to (any graph ``node_measures`` accepts, without parallel edges)
+        :param memberships: node x role DataFrame matched to the nodes of G by label; None = ``node_role_factor``.  A
+          frame such as ``transform(features_b)`` together with graph B gives the affinities of the LEARNED roles on
+          the second graph, to compare with those of the graph they were learned on.  Nothing fitted is changed
+        :param weight, mode, direction: as ``neighbor_roles``
+        :param normalize: divide every column of N by its mean over the nodes first (a column with mean 0 gives a
+          column of zeros), as ``sense_making`` does, so that a rare role compares with a common one
+        :return: DataFrame, index = the node's role, columns = its neighbours' role (the labels of `memberships`);
+          also stored as ``role_affinity_factor``
+
+        P is uploaded once; grx_neighbor_roles writes N under P^T in one feature-major block, one grx_gram pass over it
+        gives P^T P and P^T N, and the NNLS is grx_host_nnls.  A ``distributed`` extractor runs this replicated: every
+        rank holds the same factors.  ``explain()`` is the reference's stub and still raises NotImplementedError.
+        """
+        if memberships is None:
+            if self.node_role_factor is None:
+                raise ValueError('neighbor_sense needs fitted roles (call extract_role_factors first) or a memberships '
+                                 'table')
+            memberships = self.node_role_factor
+        from graphrole_amd import measures
+        K, PtP, PtN, nn = measures._neighbor_normal_equations(G, memberships, weight, mode, direction, 'neighbor_sense',
+                                                              normalize=bool(normalize))
+        Q = np.zeros_like(PtN) if K is None else K.nnls(PtP, PtN, nn)
+        self.role_affinity_factor = pd.DataFrame(Q, index=memberships.columns, columns=memberships.columns)
+        return self.role_affinity_factor
 
     def _plan(self, n_rows: int):
         """Row shards of the feature table (equal row counts: every row of the NMF passes costs the same)."""

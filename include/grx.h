@@ -36,7 +36,8 @@ extern "C" {
                                     grx_eccentricity, grx_structural_holes, grx_weighted_distances,
                                     grx_weighted_betweenness, grx_clustering, grx_square_clustering, grx_nmf_transform and
                                     grx_truss_numbers joined later under the same number (added entry points only);
-                                    so did grx_graphlet_orbits (graphlet degree vectors, orbits 0-14)
+                                    so did grx_graphlet_orbits (graphlet degree vectors, orbits 0-14) and
+                                    grx_neighbor_roles (the neighbour-role table of NeighborSense)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1267,6 +1268,40 @@ int grx_graphlet_orbits(int64_t n, const int64_t *d_row_ptr, const int32_t *d_co
                         const int32_t *d_o_col, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
                         const int64_t *d_squares, int64_t *d_orbits, int64_t *d_noninduced, int32_t *d_arc_triangles,
                         void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_neighbor_roles: the neighbour-role table of RolX NeighborSense (Henderson et al., KDD 2012, section 4), the
+ *   sparse x dense product N = A P of a CSR with the node x role memberships P.  For row i with the arcs at positions
+ *   p = row_ptr[i] .. row_ptr[i + 1] - 1
+ *     GRX_NEIGHBOR_SUM :  N[k, i] = sum_p w_p * P[col_p, k]
+ *     GRX_NEIGHBOR_MEAN:  that sum divided by D(i) = sum_p w_p; 0.0 where D(i) == 0 (a row without arcs, a row of zero
+ *                         strength): never NaN for finite input
+ *   d_w: fp64[nnz] or NULL (every w_p = 1: no product is formed and D(i) = the number of arcs, exact).
+ *   d_P: fp64, n x r row-major with leading dimension ldp >= r (P[v, k] = d_P[v * ldp + k]); 1 <= r <= GRX_MAX_ROLES.
+ *   d_out: fp64, FEATURE-major r x n with leading dimension ld_out >= n (N[k, i] = d_out[k * ld_out + i]), the layout
+ *   grx_gram reads; every entry of the r rows is overwritten, nothing beyond column n is touched.
+ *   Summation order, the same for every role k and for D(i): let d be the number of arcs of the row and S = 8 slots if
+ *   d <= 1024, S = 128 slots otherwise.  Slot s starts from +0.0 and adds the terms of the arcs row_ptr[i] + s,
+ *   row_ptr[i] + s + S, row_ptr[i] + s + 2 S, ... in that order, each product w_p * P[col_p, k] rounded on its own
+ *   before it is added (no fused multiply-add).  Then for h = S / 2, S / 4, ..., 1: slot[t] = slot[t] + slot[t + h]
+ *   for every t < h; slot[0] is the sum.  The mean is one division of that sum by D(i), itself the w_p summed in the
+ *   same slots and the same tree.  The order depends on the positions of the row's arcs only -- not on the run, the
+ *   grid or lanes_per_row -- so every output has the same bits in every call; there are no floating-point atomics.
+ *   lanes_per_row: the lanes that walk one row, S * CL.  CL = ceil(r / 2) rounded up to a power of two (1 .. 16) lanes
+ *   fetch one membership row together, two columns each; S = 1, 2, 4 or 8 physical arc slots carry the 8 slots of the
+ *   order above, 8 / S of them per lane.  0 = the library's choice (S = min(8, 32 / CL)), otherwise CL times 1, 2, 4
+ *   or 8 and at most 64; every accepted value gives the same bits.
+ *   Method: see the header of csrc/grx_neighbor_sense.hip.  Two launches, no workspace, no device -> host read;
+ *   rows longer than 1024 arcs are walked by a whole workgroup each, in the second launch.  Cost: per arc one gathered membership row of 8 r bytes.
+ *   n == 0 returns GRX_OK at once.  GRX_ERR_INVALID before any HIP call for n outside [0, 2^31), r < 1, ldp < r,
+ *   ld_out < n, another mode or lanes_per_row, or a NULL pointer (d_w excepted); GRX_ERR_UNSUPPORTED for
+ *   r > GRX_MAX_ROLES.  Column indices are trusted to lie in [0, n).
+ */
+#define GRX_NEIGHBOR_SUM 0
+#define GRX_NEIGHBOR_MEAN 1
+int grx_neighbor_roles(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
+                       const double *d_P, int64_t ldp, int r, int mode, int lanes_per_row, double *d_out,
+                       int64_t ld_out, void *stream);
 
 #ifdef __cplusplus
 }
