@@ -22,4 +22,7 @@ def __getattr__(name):
                 'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
+    if name == 'nearest_nodes':
+        from .similarity import nearest_nodes
+        return nearest_nodes
     raise AttributeError(name)

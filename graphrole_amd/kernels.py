@@ -1544,3 +1544,51 @@ def neighbor_roles(csr: DeviceCSR, P: torch.Tensor, mode: str = 'mean', w: Optio
     _lib.call('grx_neighbor_roles', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(w), _ptr(P), max(P.stride(0), r), r,
               int(mode == 'mean'), int(lanes), _ptr(out), _ld(out), _stream())
     return out[:, :n]
+
+
+SIM_QUERY_TILE = 128         # csrc/grx_similarity.hip: queries of one scan workgroup (two per lane of a wavefront),
+SIM_CANDIDATE_TILE = 64      # candidate rows staged in LDS at a time,
+SIM_MAX_SEGMENTS = 256       # most segments the library chooses (segments=0),
+SIM_SMALL_K = 16             # and the k up to which the short selection lists are compiled
+MAX_TOPK = 64                # GRX_MAX_TOPK of include/grx.h
+SIMILARITY_METRICS = {'cosine': 0, 'euclidean': 1}          # GRX_SIMILARITY_*
+
+
+def similarity_shape() -> Tuple[int, int, int]:
+    """(query tile, candidate tile, the largest `segments` the library chooses) of grx_similar_rows: the sizes at which
+    its launch shape changes."""
+    return SIM_QUERY_TILE, SIM_CANDIDATE_TILE, SIM_MAX_SEGMENTS
+
+
+def similar_rows(X: torch.Tensor, Q: Optional[torch.Tensor] = None, self_rows: Optional[torch.Tensor] = None, k: int = 10,
+                 metric: str = 'cosine', segments: int = 0, c: Optional[int] = None,
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """grx_similar_rows: (index int32[nq, k], score fp64[nq, k]) -- for every row of Q its k nearest rows of X in the
+    strict order (score nearer first, then smaller row), exactly; slots without a candidate hold -1 / NaN.  X, Q: fp64
+    device matrices [n, >= c] / [nq, >= c] row-major (leading dimension = stride(0)); c: the columns read (None = all
+    of X's).  Q=None: the rows of X query themselves and leave themselves out (self_rows = arange(n)).  self_rows:
+    int32[nq] device tensor, the row of X left out per query (-1 = none); None with a Q = nothing is left out.  metric
+    'cosine' (larger is nearer) or 'euclidean' (smaller is nearer).  segments: 0 = the library's choice; the result does
+    not depend on it.  out: (index, score) blocks [nq, >= k] to write into."""
+    if metric not in SIMILARITY_METRICS:
+        raise ValueError(f"similar_rows: metric must be 'cosine' or 'euclidean' (got {metric!r})")
+    assert X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1
+    n = int(X.shape[0])
+    c = int(X.shape[1] if c is None else c)
+    if Q is None:
+        Q = X
+        if self_rows is None and n:
+            self_rows = to_device(np.arange(n, dtype=np.int32))
+    assert Q.dtype == torch.float64 and Q.dim() == 2 and Q.stride(1) == 1
+    nq, k = int(Q.shape[0]), int(k)
+    assert self_rows is None or (self_rows.dtype == torch.int32 and self_rows.numel() >= nq and self_rows.is_contiguous())
+    if out is None:
+        out = empty((max(nq, 1), max(k, 1)), torch.int32), empty((max(nq, 1), max(k, 1)))
+    index, score = out
+    assert index.dtype == torch.int32 and score.dtype == torch.float64 and index.stride(1) == 1 and score.stride(1) == 1
+    assert _ld(index) == _ld(score) and index.shape[0] >= nq and score.shape[0] >= nq
+    ws, ws_bytes = _workspace('grx_similar_rows_workspace_bytes', n, nq, c, k, int(segments))
+    _lib.call('grx_similar_rows', n, c, _ptr(X), max(X.stride(0), c), nq, _ptr(Q), max(Q.stride(0), c), _ptr(self_rows), k,
+              SIMILARITY_METRICS[metric], int(segments), _ptr(index), _ptr(score), _ld(index), _ptr(ws), ws_bytes,
+              _stream())
+    return index[:nq, :k], score[:nq, :k]

@@ -294,6 +294,30 @@ class RoleExtractor:
         self.role_affinity_factor = pd.DataFrame(Q, index=memberships.columns, columns=memberships.columns)
         return self.role_affinity_factor
 
+    def similar_nodes(self, nodes=None, k: int = 10, metric: str = 'cosine', include_self: bool = False,
+                      memberships: Optional[pd.DataFrame] = None, candidates: Optional[pd.DataFrame] = None):
+        """
+        New (RolX structural similarity, Henderson et al., KDD 2012, section 5.2): the k nodes that play the role mix of
+        `nodes` most closely -- ``graphrole_amd.nearest_nodes`` on the memberships, an exact search on the device
+        (grx_similar_rows).
+
+        :param nodes, k, metric, include_self, candidates: as ``nearest_nodes``; ``candidates=transform(features_b)``
+          asks which nodes of a second graph resemble a node of the fitted one
+        :param memberships: the node x role table the queries come from; None = the CURRENT ``node_role_factor`` (the
+          frame is the caller's to edit, so it is uploaded at every call, as ``roles`` does)
+        :return: what ``nearest_nodes`` returns: a Series for a single node, otherwise ``(neighbors, scores)``
+
+        Nothing fitted is changed.
+        """
+        if memberships is None:
+            if self.node_role_factor is None:
+                raise ValueError('similar_nodes needs fitted roles (call extract_role_factors first) or a memberships '
+                                 'table')
+            memberships = self.node_role_factor
+        from graphrole_amd import similarity
+        return similarity.nearest_nodes(memberships, nodes, k=k, metric=metric, include_self=include_self,
+                                        candidates=candidates)
+
     def _plan(self, n_rows: int):
         """Row shards of the feature table (equal row counts: every row of the NMF passes costs the same)."""
         if not self.distributed:

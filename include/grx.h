@@ -37,7 +37,8 @@ extern "C" {
                                     grx_weighted_betweenness, grx_clustering, grx_square_clustering, grx_nmf_transform and
                                     grx_truss_numbers joined later under the same number (added entry points only);
                                     so did grx_graphlet_orbits (graphlet degree vectors, orbits 0-14) and
-                                    grx_neighbor_roles (the neighbour-role table of NeighborSense)
+                                    grx_neighbor_roles (the neighbour-role table of NeighborSense) and
+                                    grx_similar_rows (structural similarity: exact top-k nearest rows)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1302,6 +1303,44 @@ int grx_graphlet_orbits(int64_t n, const int64_t *d_row_ptr, const int32_t *d_co
 int grx_neighbor_roles(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
                        const double *d_P, int64_t ldp, int r, int mode, int lanes_per_row, double *d_out,
                        int64_t ld_out, void *stream);
+
+/*
+ * grx_similar_rows: structural similarity (Henderson et al., KDD 2012, section 5.2) -- for every query row its k
+ *   nearest candidate rows of a node x column table, exactly.  Memberships, ReFeX features or the output of a
+ *   transform: any fp64 table of 1 <= c <= GRX_MAX_ROLES columns.
+ *   d_X: the n candidates, row-major with leading dimension ldx >= c; d_Q: the nq queries, ldq >= c; d_Q may alias d_X.
+ *   d_self: int32[nq] or NULL -- the candidate row left out for query q (its own row when a table queries itself),
+ *   -1 = none.  It is left out by position: a duplicate of the query is a legitimate neighbour.
+ *     GRX_SIMILARITY_COSINE   : larger is nearer.  norm(x) = sqrt(sum_j x_j * x_j), xn_j = x_j / norm (0.0 for a row of
+ *                               norm 0: its score with anything is 0.0), score = sum_j qn_j * xn_j.
+ *     GRX_SIMILARITY_EUCLIDEAN: smaller is nearer.  Ordered by d2 = sum_j (q_j - x_j) * (q_j - x_j); the score reported
+ *                               is sqrt(d2).
+ *   Arithmetic: every sum runs j = 0 .. c - 1 from +0.0, every product and difference is rounded on its own before it
+ *   is added (no fused multiply-add), the normalisation is one division per element by the rounded norm.  So the score
+ *   of a pair has the same bits for every `segments`, in every run, and score(a, b) == score(b, a) bitwise.
+ *   d_index int32, d_score fp64: [nq, k] row-major with leading dimension ld_out >= k.  Row q holds the first k
+ *   candidates in the strict total order (score nearer first, then smaller candidate row), d_self[q] left out; the
+ *   result is unique.  With fewer than k candidates the remaining slots hold index -1 and score NaN.  Nothing beyond
+ *   column k of a row is touched.  No floating-point atomics.
+ *   segments: 0 = the library's choice; otherwise the candidates are split into that many contiguous ranges (at most one
+ *   per 64-row candidate tile, at most 1024), each scanned by its own workgroups, and the per-range lists are merged by
+ *   one more launch.  This is what fills the chip when nq is small.  The result does not depend on it.
+ *   d_workspace: grx_similar_rows_workspace_bytes(n, nq, c, k, segments) bytes: the normalised, zero-padded copies of X
+ *   and Q and the lists of the segments.
+ *   Non-finite input is the caller's to refuse; a NaN key is never taken, nothing hangs or leaves its buffers.
+ *   Limits: n, nq < 2^31, 1 <= k <= GRX_MAX_TOPK.  nq == 0 returns GRX_OK at once; n == 0 fills the slots that exist
+ *   (index -1, score NaN: one small launch, none when the outputs are NULL) and returns GRX_OK.  GRX_ERR_UNSUPPORTED for
+ *   c > GRX_MAX_ROLES; GRX_ERR_INVALID before any HIP call for n, nq, k or c < 1 out of range, ldx < c, ldq < c,
+ *   ld_out < k, another metric, segments < 0, a workspace that is too small, or a NULL pointer (d_self excepted) with
+ *   n and nq positive.  Method, LDS budget and bound: the header of csrc/grx_similarity.hip.
+ */
+#define GRX_MAX_TOPK 64
+#define GRX_SIMILARITY_COSINE 0
+#define GRX_SIMILARITY_EUCLIDEAN 1
+size_t grx_similar_rows_workspace_bytes(int64_t n, int64_t nq, int c, int k, int segments);
+int grx_similar_rows(int64_t n, int c, const double *d_X, int64_t ldx, int64_t nq, const double *d_Q, int64_t ldq,
+                     const int32_t *d_self, int k, int metric, int segments, int32_t *d_index, double *d_score,
+                     int64_t ld_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
