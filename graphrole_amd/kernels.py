@@ -22,6 +22,32 @@ RJ_ROW_MAX_WG = 2048     # workgroups of its row kernels (256 / lanes rows per w
 RJ_ARC_MAX_WG = 8192     # and of its per-arc kernel (256 / lanes arcs per workgroup pass)
 SQ_WAVE_MAX_WEDGES = 768     # csrc/grx_square_clustering.hip: rows with at most this many wedges count in a one-wavefront
 SQ_LDS_MAX_WEDGES = 3072     # LDS table, up to this many in a four-wavefront one, above in dense counters in HBM
+# The caps of the other grid-stride launches, grx_grid(items, per_block, cap): a launch takes a second trip of its loop
+# when items > cap * per_block.  tests/test_gpu_second_trip.py sizes its graphs by these copies and
+# tests/test_tiled_graphs_cpu.py reads every value back from the source named here.
+TR_SWEEP_MAX_WG = 2048       # csrc/grx_truss.hip: workgroups of the per-arc sweeps (256 arcs each)
+TR_PEEL_MAX_WG = 2048        # and of the peel (256 / lanes frontier edges each)
+GL_K4_MAX_WG = 8192          # csrc/grx_graphlets.hip: workgroups of the 4-clique kernel (256 / lanes arcs each)
+SQ_WAVE_MAX_WG = 8192        # csrc/grx_square_clustering.hip: workgroups of the wave tier (64 rows each),
+SQ_LDS_MAX_WG = 1024         # of the LDS tier (256 rows each)
+SQ_DENSE_WG = 128            # and of the dense tier (1024 rows each)
+BC_BLOCK = 256               # csrc/grx_biconnected.hip: threads per workgroup
+BC_MAX_BLOCKS = 2048         # and workgroups of its per-node launches
+SP_BLOCK = 256               # csrc/grx_relax.h: threads per workgroup of the relaxation rounds,
+SP_MAX_ROW_BLOCKS = 8192     # their workgroups (256 / batch rows each)
+SP_MAX_BLOCKS = 2048         # csrc/grx_sssp.hip: workgroups of its per-node launches
+WB_BLOCK = 256               # csrc/grx_weighted_betweenness.hip: threads per workgroup,
+WB_MAX_ROW_BLOCKS = 8192     # workgroups of the row kernels (256 / batch rows each)
+WB_MAX_BLOCKS = 2048         # and of the per-element launches
+CL_BLOCK = 256               # csrc/grx_closeness.hip (grx_distance_sums, grx_eccentricity): threads per workgroup
+CL_MAX_ROW_BLOCKS = 8192     # and workgroups of the level kernels (256 / words rows each)
+NS_BLOCK = 256               # csrc/grx_neighbor_sense.hip: threads per workgroup,
+NS_MAX_WG = 8192             # workgroups of the row kernel (256 / lanes rows each)
+NS_LONG_MAX_WG = 1024        # and of the long-row kernel (256 rows looked at each)
+TRANSFORM_BLOCK = 256        # TR_BLOCK of csrc/grx_transform.hip: rows of a workgroup of the row kernels
+TRANSFORM_MAX_GRID = 2048    # TR_MAX_GRID there (GRX_NUM_CU * 8): their workgroups
+SIM_BLOCK = 256              # csrc/grx_similarity.hip: threads (rows / slots) per workgroup of the prepare and fill kernels
+SIM_ROW_MAX_WG = 2048        # and the literal cap of those launches
 
 
 def _ptr(t: Optional[torch.Tensor]):

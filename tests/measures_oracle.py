@@ -272,6 +272,7 @@ GRAPHS = {
     # a self-loop on every one of the first 3 ordinary nodes of a dangling-free graph
     'self_loop': dict(seed=34, n=50, avg_degree=6, self_loops=3),
     # the row loop takes a second trip (n > 2048 * 256 / L) for L = 32 and L = 4, the element loops at n > 2048 * 256
+    # (the second trips of the other measures' launches: tests/test_gpu_second_trip.py, which lists all such tests)
     'rows32': dict(seed=41, n=2048 * 8 + 5, avg_degree=5),
     'rows4': dict(seed=42, n=2048 * 64 + 9, avg_degree=5, weighted=True),
     'elements': dict(seed=43, n=2048 * 256 + 77, avg_degree=4, hubs=(300,)),

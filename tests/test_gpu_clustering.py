@@ -147,7 +147,8 @@ def test_zero_weights():
 def test_second_trip_of_the_grid_stride_loops():
     """BA 60 000 / m = 5 against the sparse oracle.  With 32 lanes a workgroup pass takes RJ_BLOCK / 32 = 8 rows or
     arcs, so the row kernels (cap RJ_ROW_MAX_WG) and the per-arc kernel (cap RJ_ARC_MAX_WG) both wrap; with the CSR's
-    own 4 lanes the per-arc kernel wraps."""
+    own 4 lanes the per-arc kernel wraps.  (Every other second-trip test of the suite is listed at the top of
+    tests/test_gpu_second_trip.py.)"""
     from graphrole_amd import kernels as K
     n, row_ptr, col, fwd = _ba60000()
     nnz = len(col)
