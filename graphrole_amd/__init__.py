@@ -25,4 +25,10 @@ def __getattr__(name):
     if name == 'nearest_nodes':
         from .similarity import nearest_nodes
         return nearest_nodes
+    if name in ('connected_components', 'weakly_connected_components', 'strongly_connected_components',
+                'number_connected_components', 'number_weakly_connected_components',
+                'number_strongly_connected_components', 'is_connected', 'is_weakly_connected', 'is_strongly_connected',
+                'component_table', 'largest_component', 'descendants', 'ancestors', 'bow_tie'):
+        from . import components
+        return getattr(components, name)
     raise AttributeError(name)

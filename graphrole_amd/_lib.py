@@ -292,6 +292,13 @@ _SIGNATURES = {
     'grx_similar_rows_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
     'grx_similar_rows': (c_int, [c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int,
                                  c_int, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    'grx_components_workspace_bytes': (c_size_t, [c_int64]),
+    'grx_components': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                               c_int64, c_int, c_int, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_void_p,
+                               c_size_t, c_void_p]),
+    'grx_reachable_workspace_bytes': (c_size_t, [c_int64]),
+    'grx_reachable': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, POINTER(c_int64),
+                              POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -30,6 +30,7 @@
 // graph (a path) is bound by launch latency, D launches per sweep; that case is not optimised.
 // int32 ids, integer vector atomics only, no floating point.
 #include "grx_common.h"
+#include "grx_unionfind.h"
 
 #include <algorithm>
 #include <climits>
@@ -79,37 +80,11 @@ BcWs carve(void *base, int64_t n)
     return ws;
 }
 
-// words other workgroups update while this kernel runs are read and written past the L1
-__device__ __forceinline__ int ld(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// union-find with p[x] <= x: the root of a set is its smallest member that was ever hooked under nothing.  A vertex
-// that has a parent keeps one for good, and every value ever stored in p[x] is a member of x's set below x, so a
-// stale read only lengthens the walk.
-__device__ __forceinline__ int uf_find(int32_t *p, int x)
-{
-    int cur = ld(p + x);
-    if (cur != x) {
-        int prev = x, next;
-        while (cur > (next = ld(p + cur))) {                 // pointer jumping: prev skips cur
-            st(p + prev, next);
-            prev = cur;
-            cur = next;
-        }
-    }
-    return cur;
-}
-
-__device__ __forceinline__ void uf_union(int32_t *p, int a, int b)
-{
-    int ra = uf_find(p, a), rb = uf_find(p, b);
-    while (ra != rb) {
-        if (ra < rb) { const int t = ra; ra = rb; rb = t; }
-        const int old = atomicCAS(p + ra, ra, rb);           // hooks ra under the smaller rb only while ra is a root
-        if (old == ra) break;
-        ra = old;                                            // ra got a parent meanwhile: go on from there
-    }
-}
+// the union-find of steps 1 and 6 and its loads and stores past the L1: grx_unionfind.h (shared with grx_components.hip)
+__device__ __forceinline__ int ld(const int32_t *p) { return grx_ld32(p); }
+__device__ __forceinline__ void st(int32_t *p, int v) { grx_st32(p, v); }
+__device__ __forceinline__ int uf_find(int32_t *p, int x) { return grx_uf_find(p, x); }
+__device__ __forceinline__ void uf_union(int32_t *p, int a, int b) { grx_uf_union(p, a, b); }
 
 // exclusive scan of x over the workgroup; *total = the sum.  lds: BC_WAVES ints
 __device__ __forceinline__ int block_excl_scan(int x, int *total, int *lds)

@@ -48,6 +48,11 @@ TRANSFORM_BLOCK = 256        # TR_BLOCK of csrc/grx_transform.hip: rows of a wor
 TRANSFORM_MAX_GRID = 2048    # TR_MAX_GRID there (GRX_NUM_CU * 8): their workgroups
 SIM_BLOCK = 256              # csrc/grx_similarity.hip: threads (rows / slots) per workgroup of the prepare and fill kernels
 SIM_ROW_MAX_WG = 2048        # and the literal cap of those launches
+CP_BLOCK = 256               # csrc/grx_components.hip: threads per workgroup,
+CP_GROUP = 8                 # lanes per row of the row kernels (256 / 8 rows per workgroup pass),
+CP_MAX_BLOCKS = 2048         # workgroups of the per-node launches
+CP_MAX_ROW_BLOCKS = 8192     # and of the row kernels
+CP_ROUND_BATCH = 16          # rounds (levels) enqueued between two read-backs
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1434,6 +1439,55 @@ def _hubs_for(csr: DeviceCSR, lanes: Optional[int]) -> tuple:
     rows = np.nonzero(np.diff(csr._host[0]) > HUB_FACTOR * int(lanes))[0].astype(np.int32)
     hub_rows = torch.from_numpy(rows).to(device()) if len(rows) else None
     return _ptr(hub_rows), int(len(rows)), int(lanes), hub_rows
+
+COMPONENT_MODES = {'connected': 0, 'weak': 1, 'strong': 2}       # GRX_COMPONENTS_*
+
+
+def components(csr: DeviceCSR, in_csr: Optional[DeviceCSR] = None, mode: str = 'connected', want_size: bool = True,
+               lanes: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], int, int]:
+    """grx_components on the CSR of a graph's distinct arcs (self-loops allowed): (label int32[n] = the smallest row
+    of every row's component, size int64[n] = the rows in it, n_components, rounds).  mode 'connected': csr is the
+    symmetric CSR of an undirected graph; 'weak': the out-adjacency of a directed graph alone (in_csr is not passed on);
+    'strong': csr and in_csr, its transpose; rounds = the trim / colour / close rounds run (0 for the other modes).
+    want_size=False passes NULL for size (None then).  lanes = lanes per row (None = each CSR's own), with the hub
+    lists of that width."""
+    if mode not in COMPONENT_MODES:
+        raise ValueError(f'mode must be one of {sorted(COMPONENT_MODES)}, got {mode!r}')
+    if mode == 'strong' and in_csr is None:
+        raise _lib.GrxInvalid("components(mode='strong') needs the in-adjacency (in_csr) as well")
+    n = csr.n
+    ws, ws_bytes = _workspace('grx_components_workspace_bytes', n)
+    label = torch.empty(max(n, 1), dtype=torch.int32, device=device())
+    size = torch.empty(max(n, 1), dtype=torch.int64, device=device()) if want_size else None
+    hubs = _hubs_for(csr, lanes)
+    in_hubs = _hubs_for(in_csr, lanes) if mode == 'strong' else (None, 0, 0, None)
+    in_ptrs = (_ptr(in_csr.row_ptr), _ptr(in_csr.col)) if mode == 'strong' else (None, None)
+    n_components, rounds = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call('grx_components', n, _ptr(csr.row_ptr), _ptr(csr.col), hubs[0], hubs[1], hubs[2], in_ptrs[0], in_ptrs[1],
+              in_hubs[0], in_hubs[1], in_hubs[2], COMPONENT_MODES[mode], _ptr(label), _ptr(size),
+              ctypes.byref(n_components), ctypes.byref(rounds), _ptr(ws), ws_bytes, _stream())
+    return label, size, int(n_components.value), int(rounds.value)
+
+
+def reachable(csr: DeviceCSR, flag, lanes: Optional[int] = None) -> Tuple[torch.Tensor, int, int]:
+    """grx_reachable: the closure of the seeds along csr's arcs.  flag: int32[n] (a host array, or a device tensor that
+    is updated in place), non-zero = seed.  (flag int32[n] on the device = 1 on every seed and every row reachable from
+    one, count = the number of ones, levels = the depth reached).  The out-adjacency gives descendants, the
+    in-adjacency ancestors."""
+    n = csr.n
+    if not isinstance(flag, torch.Tensor):
+        host = np.ascontiguousarray(flag, dtype=np.int32)
+        flag = torch.empty(max(n, 1), dtype=torch.int32, device=device())
+        if n:
+            flag[:n].copy_(torch.from_numpy(host[:n]))
+    if flag.dtype != torch.int32 or flag.numel() < n or not flag.is_contiguous():
+        raise ValueError('reachable: flag must be a contiguous int32 tensor of at least n entries')
+    ws, ws_bytes = _workspace('grx_reachable_workspace_bytes', n)
+    hubs = _hubs_for(csr, lanes)
+    count, levels = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call('grx_reachable', n, _ptr(csr.row_ptr), _ptr(csr.col), hubs[0], hubs[1], hubs[2], _ptr(flag),
+              ctypes.byref(count), ctypes.byref(levels), _ptr(ws), ws_bytes, _stream())
+    return flag, int(count.value), int(levels.value)
 
 
 def structural_holes(csr: DeviceCSR, z: Optional[torch.Tensor] = None, out_row_ptr: Optional[torch.Tensor] = None,

@@ -38,7 +38,8 @@ extern "C" {
                                     grx_truss_numbers joined later under the same number (added entry points only);
                                     so did grx_graphlet_orbits (graphlet degree vectors, orbits 0-14) and
                                     grx_neighbor_roles (the neighbour-role table of NeighborSense) and
-                                    grx_similar_rows (structural similarity: exact top-k nearest rows)
+                                    grx_similar_rows (structural similarity: exact top-k nearest rows) and
+                                    grx_components / grx_reachable (connected, weak and strong components, closures)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1341,6 +1342,51 @@ size_t grx_similar_rows_workspace_bytes(int64_t n, int64_t nq, int c, int k, int
 int grx_similar_rows(int64_t n, int c, const double *d_X, int64_t ldx, int64_t nq, const double *d_Q, int64_t ldq,
                      const int32_t *d_self, int k, int metric, int segments, int32_t *d_index, double *d_score,
                      int64_t ld_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_components: the connected components of an undirected graph, or the weakly or the strongly connected components
+ *   of a directed one -- networkx.connected_components, weakly_connected_components, strongly_connected_components
+ *   (networkx/algorithms/components) -- as one label per node.
+ *   d_row_ptr / d_col: the CSR of the graph's distinct arcs, rows in any order; self-loop entries are allowed and change
+ *   nothing; weights are not read.  Rows longer than GRX_HUB_FACTOR * lanes_per_row (in_lanes_per_row) must be listed
+ *   in d_hub_rows (d_in_hub_rows).
+ *   mode: GRX_COMPONENTS_CONNECTED -- the CSR is symmetric (every edge from both ends), all d_in_* NULL / 0;
+ *         GRX_COMPONENTS_WEAK      -- the out-CSR of a directed graph alone; d_in_* are ignored and may be NULL;
+ *         GRX_COMPONENTS_STRONG    -- the out-CSR and d_in_row_ptr / d_in_col, its transpose (GRX_ERR_INVALID without).
+ *   Method: CONNECTED and WEAK by the lock-free union-find of grx_biconnected (hook the larger root under the smaller,
+ *   pointer jumping, flatten); STRONG by trim and colour (Orzan 2004; Barnat et al. 2011): trim the nodes without an
+ *   alive in- or out-neighbour, propagate the smallest id forward to a fixed point, close backward from the nodes that
+ *   kept their own id inside their colour, remove what was reached, repeat -- device-steered rounds, 16 per read-back;
+ *   see the header of csrc/grx_components.hip for the rounds, the bound and the known worst case (a chain of small
+ *   components with ascending ids: one outer iteration per component).
+ *   d_label: int32[n], overwritten: the smallest row id of v's component.
+ *   d_size:  int64[n] or NULL: the number of rows in v's component.
+ *   n_components: HOST int64 or NULL (reading it waits for the stream).
+ *   h_rounds: HOST int64 or NULL: the number of rounds STRONG ran (0 for the other modes).
+ *   Exact (integers only; vector integer atomics whose results do not depend on their order): every output has the
+ *   same bits in every run and for every lane width, and is the same partition under every relabelling of the rows.
+ *   0 <= n < 2^31; n == 0 returns GRX_OK at once with 0 components.  d_workspace: grx_components_workspace_bytes(n)
+ *   bytes (about 16 n).  STRONG waits for the stream.
+ *
+ * grx_reachable: the closure of a seed set along the CSR's arcs.  d_flag: int32[n], in and out: non-zero on entry marks
+ *   a seed; on return 1 for every seed and every node reachable from one, 0 elsewhere (descendants with the out-CSR,
+ *   ancestors with the in-CSR).  Level-synchronous, 16 levels per read-back.  h_count: HOST int64 or NULL, the number
+ *   of ones; h_levels: HOST int64 or NULL, the depth reached (0 when the seeds reach nothing new).  Conventions, limits
+ *   and exactness as above.  d_workspace: grx_reachable_workspace_bytes(n) bytes (about 4 n).  The call waits for the
+ *   stream.
+ */
+enum { GRX_COMPONENTS_CONNECTED = 0, GRX_COMPONENTS_WEAK = 1, GRX_COMPONENTS_STRONG = 2 };
+size_t grx_components_workspace_bytes(int64_t n);
+int grx_components(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                   int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+                   const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, int mode,
+                   int32_t *d_label, int64_t *d_size, int64_t *n_components, int64_t *h_rounds,
+                   void *d_workspace, size_t workspace_bytes, void *stream);
+
+size_t grx_reachable_workspace_bytes(int64_t n);
+int grx_reachable(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                  int64_t n_hub_rows, int lanes_per_row, int32_t *d_flag, int64_t *h_count, int64_t *h_levels,
+                  void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
