@@ -21,13 +21,16 @@
 // At the end harmonic(v) = harm(v) 2^-84, rounded once to nearest-even: the correctly rounded sum of the fp64
 // terms fl(1 / d), the same bits for every W, source order and run.  Integer arithmetic only; no floating-point
 // atomics (the source bits are set with integer atomicOr).
-// grx_eccentricity (below grx_distance_sums' kernels) runs the same BFS with a maximum in place of the sums: the
-// eccentricity of every source, the per-target maximum distance and the eccentricity bounds of Takes and Kosters.
+// The traversal is written once (ms_level_kernel, ms_level_hub_kernel and the host's ms_bfs: the level core below);
+// what the writer adds is a body.  grx_distance_sums runs it with the sums above; grx_eccentricity with two more
+// bodies that take a maximum in place of the sums: the eccentricity of every source, the per-target maximum distance
+// and the eccentricity bounds of Takes and Kosters.
 #pragma clang fp contract(off)
 
 #include "grx_common.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -55,27 +58,29 @@ int choose_words(int64_t n, int words, int64_t n_sources)
     return w;
 }
 
-size_t ws_bytes(int64_t n, int W)
+// the workspace: visited | f0 | f1 (uint64[n W] each) | harm (uint64[2 n]; the distance sums only) | control words
+size_t ws_bytes(int64_t n, int W, bool with_harm)
 {
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    return 3 * grx_align_up(nn * (size_t)W * 8, 256) + grx_align_up(nn * 16, 256) + 256;
+    return 3 * grx_align_up(nn * (size_t)W * 8, 256) + (with_harm ? grx_align_up(nn * 16, 256) : 0) + 256;
 }
 
-struct ClWs {
+struct MsWs {
     uint64_t *visited, *f0, *f1;
-    uint64_t *harm;                                          // (lo, hi) per node
+    uint64_t *harm;                                          // (lo, hi) per node; null without with_harm
     int32_t *ctrl;
 };
 
-ClWs carve(void *base, int64_t n, int W)
+MsWs carve(void *base, int64_t n, int W, bool with_harm)
 {
-    const size_t nn = (size_t)(n > 0 ? n : 1);
+    const size_t nn = (size_t)(n > 0 ? n : 1), mask = grx_align_up(nn * (size_t)W * 8, 256);
     char *p = reinterpret_cast<char *>(base);
-    ClWs ws;
-    ws.visited = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
-    ws.f0 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
-    ws.f1 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
-    ws.harm = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * 16, 256);
+    MsWs ws;
+    ws.visited = reinterpret_cast<uint64_t *>(p); p += mask;
+    ws.f0 = reinterpret_cast<uint64_t *>(p); p += mask;
+    ws.f1 = reinterpret_cast<uint64_t *>(p); p += mask;
+    ws.harm = with_harm ? reinterpret_cast<uint64_t *>(p) : nullptr;
+    if (with_harm) p += grx_align_up(nn * 16, 256);
     ws.ctrl = reinterpret_cast<int32_t *>(p);
     return ws;
 }
@@ -116,24 +121,6 @@ __device__ __forceinline__ uint64_t pull_words(int64_t b, int64_t e, int step, c
     return acc & want;
 }
 
-// the node's writer: c newly reached sources at distance d
-__device__ __forceinline__ void add_level(int64_t v, int c, int d, int64_t *__restrict__ reach,
-                                          int64_t *__restrict__ dsum, uint64_t *__restrict__ harm)
-{
-    reach[v] += c;
-    dsum[v] += (int64_t)d * c;
-    // fl(1 / d) = m 2^(e - 52) with a 53-bit m and -31 <= e <= 0 (1 <= d < 2^31): times 2^84 is m << (e + 32)
-    const double r = 1.0 / (double)d;
-    const uint64_t bits = (uint64_t)__double_as_longlong(r);
-    const int e = (int)((bits >> 52) & 0x7ff) - 1023;
-    const uint64_t m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
-    const unsigned __int128 q = (unsigned __int128)m << (e + 32);
-    unsigned __int128 h = ((unsigned __int128)harm[2 * v + 1] << 64) | harm[2 * v];
-    h += (unsigned __int128)(uint64_t)c * q;
-    harm[2 * v] = (uint64_t)h;
-    harm[2 * v + 1] = (uint64_t)(h >> 64);
-}
-
 // lane b < count: bit b of source s_b's visited and frontier words (integer atomics: one node may be the source of
 // several lanes of a word); level 0
 __global__ __launch_bounds__(CL_BLOCK) void cl_source_init_kernel(int64_t n, int W, int count,
@@ -153,65 +140,80 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_source_init_kernel(int64_t n, int
     if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl[GRX_CT_DONE] = 0; ctrl[GRX_CT_LEVEL] = 0; ctrl[GRX_CT_FOUND] = 0; }
 }
 
+// ---- the level core: one BFS level over bodies -----------------------------------------------------------------
+// Frontier selection, the pull, the visited / next stores, the hub rows' OR tree and the `found` flag are the two
+// kernels below; what a node does with its new source bits is a body: a struct of kernel arguments (a template over W)
+// with
+//   struct Shared;                                           LDS of the row kernel
+//   struct Acc;                                              what a thread carries across its nodes, zero-initialised
+//   struct View;                                             what node() reads besides the kernel arguments
+//   View row_begin(Shared &sh, int count) const;             row kernel, every thread, before the first node (with a
+//                                                            barrier of its own after what it writes)
+//   View hub_begin(const uint64_t *part, int d) const;       hub kernel, every thread: part[w] = word w of the hub's
+//                                                            new source bits (LDS)
+//   bool node(int64_t v, uint64_t nw, bool writer, int d, int w, View view, Acc &a) const;
+//                                                            nw = word w of v's new source bits, at distance d (0 in a
+//                                                            lane that holds no word of a node of this kernel).  Every
+//                                                            lane of the wavefront calls it: the group reductions see
+//                                                            them all.  `writer`: the one lane per node that updates
+//                                                            v's outputs; true from that lane when it did
+//   void row_end(Shared &sh, const Acc &a, int d, int w) const;    row kernel, every thread, after the last node
+// The bodies are template arguments, so every call inlines.
+
 // one level, rows up to hub_degree arcs: W lanes per node, CL_BLOCK / W nodes per workgroup and grid step
-template <int W>
-__global__ __launch_bounds__(CL_BLOCK) void cl_level_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+template <int W, class Body>
+__global__ __launch_bounds__(CL_BLOCK) void ms_level_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
                                                             const int32_t *__restrict__ col, int64_t hub_degree,
                                                             int count, uint64_t *__restrict__ visited,
                                                             uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
-                                                            int64_t *__restrict__ reach, int64_t *__restrict__ dsum,
-                                                            uint64_t *__restrict__ harm, int32_t *__restrict__ ctrl)
+                                                            int32_t *__restrict__ ctrl, const Body body)
 {
     constexpr int GROUPS = CL_BLOCK / W;
-    if (ctrl[GRX_CT_DONE]) return;
-    const int l = ctrl[GRX_CT_LEVEL];
+    __shared__ typename Body::Shared sh;
+    if (ctrl[GRX_CT_DONE]) return;                          // the same in every lane of the launch
+    const int l = ctrl[GRX_CT_LEVEL], d = l + 1;
     const uint64_t *F = (l & 1) ? f1 : f0;
     uint64_t *Fn = (l & 1) ? f0 : f1;
     const int w = threadIdx.x % W;
     const uint64_t active = active_mask(count, w);
-    int found = 0;
-    // the trip count is the same in every lane of the workgroup: the group sums below see every lane
+    const typename Body::View view = body.row_begin(sh, count);
+    int found = 0;                                          // an int: a bool is kept as a lane mask, 2 SGPRs more
+    typename Body::Acc acc{};
+    // the trip count is the same in every lane of the workgroup: the group reductions of the body see every lane
     for (int64_t first = (int64_t)blockIdx.x * GROUPS; first < n; first += (int64_t)gridDim.x * GROUPS) {
         const int64_t v = first + threadIdx.x / W;
         bool mine = false;
-        int c = 0;
+        uint64_t nw = 0;
         if (v < n) {
             const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-            if (e - b <= hub_degree) {                      // longer rows: cl_level_hub_kernel
+            if (e - b <= hub_degree) {                      // longer rows: ms_level_hub_kernel
                 mine = true;
                 const int64_t cell = v * W + w;
                 const uint64_t vw = visited[cell];
-                const uint64_t nw = pull_words<W>(b, e, 1, col, F, w, active & ~vw);
+                nw = pull_words<W>(b, e, 1, col, F, w, active & ~vw);
                 Fn[cell] = nw;
                 if (nw) visited[cell] = vw | nw;
-                c = __popcll(nw);
             }
         }
-        c = group_sum<W>(c);
-        if (mine && w == 0 && c) {
-            add_level(v, c, l + 1, reach, dsum, harm);
-            found = 1;
-        }
+        if (body.node(v, nw, mine && w == 0, d, w, view, acc)) found = 1;
     }
     if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[GRX_CT_FOUND] = 1;
+    body.row_end(sh, acc, d, w);
 }
 
 // one level, hub rows: one workgroup per hub row; CL_BLOCK / W lane groups take every (CL_BLOCK / W)-th arc
-template <int W>
-__global__ __launch_bounds__(CL_BLOCK) void cl_level_hub_kernel(const int64_t *__restrict__ row_ptr,
+template <int W, class Body>
+__global__ __launch_bounds__(CL_BLOCK) void ms_level_hub_kernel(const int64_t *__restrict__ row_ptr,
                                                                 const int32_t *__restrict__ col,
                                                                 const int32_t *__restrict__ hub_rows, int count,
                                                                 uint64_t *__restrict__ visited,
                                                                 uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
-                                                                int64_t *__restrict__ reach,
-                                                                int64_t *__restrict__ dsum,
-                                                                uint64_t *__restrict__ harm,
-                                                                int32_t *__restrict__ ctrl)
+                                                                int32_t *__restrict__ ctrl, const Body body)
 {
     constexpr int GROUPS = CL_BLOCK / W;
     __shared__ uint64_t part[CL_BLOCK];
     if (ctrl[GRX_CT_DONE]) return;
-    const int l = ctrl[GRX_CT_LEVEL];
+    const int l = ctrl[GRX_CT_LEVEL], d = l + 1;
     const uint64_t *F = (l & 1) ? f1 : f0;
     uint64_t *Fn = (l & 1) ? f0 : f1;
     const int t = threadIdx.x, w = t % W;
@@ -225,18 +227,103 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_level_hub_kernel(const int64_t *_
         if (t < s) part[t] |= part[t + s];
         __syncthreads();
     }
+    const typename Body::View view = body.hub_begin(part, d);
     if (t >= GRX_WAVE) return;
     const uint64_t nw = t < W ? part[t] : 0;
-    const int c = group_sum<W>(__popcll(nw));
     if (t < W) {
         Fn[cell] = nw;
         if (nw) visited[cell] = vw | nw;
     }
-    if (t == 0 && c) {
-        add_level(v, c, l + 1, reach, dsum, harm);
-        ctrl[GRX_CT_FOUND] = 1;
+    typename Body::Acc acc{};
+    if (body.node(v, nw, t == 0, d, w, view, acc)) ctrl[GRX_CT_FOUND] = 1;
+}
+
+// the graph and the sources of a call
+struct MsArgs {
+    int64_t n;
+    const int64_t *row_ptr;
+    const int32_t *col;
+    const int32_t *hub_rows;
+    int64_t n_hub_rows, hub_degree;
+    const int32_t *sources;
+    int64_t n_sources;
+};
+
+// one BFS from the batch of `count` <= 64 W sources at src: clears the masks, seeds level 0 and runs the levels.
+// `what`: the refusal of grx_run_rounds, with the caller's name
+template <int W, class Body>
+int ms_bfs(const char *what, const MsArgs &a, const MsWs &ws, const int32_t *src, int count, const Body &body,
+           hipStream_t st)
+{
+    const int64_t n = a.n;
+    const unsigned row_blocks = grx_grid(n, CL_BLOCK / W, CL_MAX_ROW_BLOCKS);
+    grx_fill64(ws.visited, n * W, 0, st);
+    grx_fill64(ws.f0, n * W, 0, st);
+    cl_source_init_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(n, W, count, src, ws.visited,
+                                                                                        ws.f0, ws.ctrl);
+    GRX_LAUNCH_CHECK();
+    int32_t h[2];
+    // a BFS has at most n - 1 levels; one more launch finds the empty frontier
+    return grx_run_rounds(what, CL_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
+        if (a.n_hub_rows)
+            ms_level_hub_kernel<W><<<(unsigned)a.n_hub_rows, CL_BLOCK, 0, st>>>(
+                a.row_ptr, a.col, a.hub_rows, count, ws.visited, ws.f0, ws.f1, ws.ctrl, body);
+        ms_level_kernel<W><<<row_blocks, CL_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.hub_degree, count, ws.visited,
+                                                            ws.f0, ws.f1, ws.ctrl, body);
+        return grx_frontier_advance(ws.ctrl, st);
+    });
+}
+
+// f(std::integral_constant<int, W>) for the W of a call
+template <class F>
+int ms_with_words(int W, F f)
+{
+    switch (W) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
     }
 }
+
+// ---- distance sums (grx_distance_sums) ---------------------------------------------------------------------------
+// the node's writer: c newly reached sources at distance d
+__device__ __forceinline__ void add_level(int64_t v, int c, int d, int64_t *__restrict__ reach,
+                                          int64_t *__restrict__ dsum, uint64_t *__restrict__ harm)
+{
+    reach[v] += c;
+    dsum[v] += (int64_t)d * c;
+    // fl(1 / d) = m 2^(e - 52) with a 53-bit m and -31 <= e <= 0 (1 <= d < 2^31): times 2^84 is m << (e + 32)
+    const double r = 1.0 / (double)d;
+    const uint64_t bits = (uint64_t)__double_as_longlong(r);
+    const int e = (int)((bits >> 52) & 0x7ff) - 1023;
+    const uint64_t m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
+    const unsigned __int128 q = (unsigned __int128)m << (e + 32);
+    unsigned __int128 h = ((unsigned __int128)harm[2 * v + 1] << 64) | harm[2 * v];
+    h += (unsigned __int128)(uint64_t)c * q;
+    harm[2 * v] = (uint64_t)h;
+    harm[2 * v + 1] = (uint64_t)(h >> 64);
+}
+
+template <int W>
+struct cl_sums {
+    int64_t *__restrict__ reach, *__restrict__ dsum;
+    uint64_t *__restrict__ harm;
+    struct Shared {};
+    struct Acc {};
+    struct View {};
+    __device__ __forceinline__ View row_begin(Shared &, int) const { return {}; }
+    __device__ __forceinline__ View hub_begin(const uint64_t *, int) const { return {}; }
+    __device__ __forceinline__ bool node(int64_t v, uint64_t nw, bool writer, int d, int, View, Acc &) const
+    {
+        const int c = group_sum<W>(__popcll(nw));
+        if (!(writer && c)) return false;
+        add_level(v, c, d, reach, dsum, harm);
+        return true;
+    }
+    __device__ __forceinline__ void row_end(Shared &, const Acc &, int, int) const {}
+};
 
 // harmonic(v) = harm(v) 2^-84, rounded once to nearest-even (by hand: the top 53 bits plus the rounding bits below)
 __global__ __launch_bounds__(CL_BLOCK) void cl_harmonic_kernel(int64_t n, const uint64_t *__restrict__ harm,
@@ -262,53 +349,22 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_harmonic_kernel(int64_t n, const 
     }
 }
 
-struct Args {
-    int64_t n;
-    const int64_t *row_ptr;
-    const int32_t *col;
-    const int32_t *hub_rows;
-    int64_t n_hub_rows, hub_degree;
-    const int32_t *sources;
-    int64_t n_sources;
-    int64_t *reach, *dsum;
-    double *harmonic;
-};
-
 template <int W>
-int run(const Args &a, const ClWs &ws, hipStream_t st)
+int sums_run(const MsArgs &a, const MsWs &ws, int64_t *reach, int64_t *dsum, double *harmonic, hipStream_t st)
 {
-    const int64_t n = a.n;
-    const unsigned row_blocks = grx_grid(n, CL_BLOCK / W, CL_MAX_ROW_BLOCKS);
-    const int64_t cells = n * W;
     for (int64_t first = 0; first < a.n_sources; first += 64 * W) {
         const int count = (int)std::min<int64_t>(64 * W, a.n_sources - first);
-        grx_fill64(ws.visited, cells, 0, st);
-        grx_fill64(ws.f0, cells, 0, st);
-        cl_source_init_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
-            n, W, count, a.sources + first, ws.visited, ws.f0, ws.ctrl);
-        GRX_LAUNCH_CHECK();
-        int32_t h[2];
-        // a BFS has at most n - 1 levels; one more launch finds the empty frontier
-        const int rc = grx_run_rounds(
-            "grx_distance_sums: the BFS did not end after %lld levels", CL_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
-                if (a.n_hub_rows)
-                    cl_level_hub_kernel<W><<<(unsigned)a.n_hub_rows, CL_BLOCK, 0, st>>>(
-                        a.row_ptr, a.col, a.hub_rows, count, ws.visited, ws.f0, ws.f1, a.reach, a.dsum, ws.harm,
-                        ws.ctrl);
-                cl_level_kernel<W><<<row_blocks, CL_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.hub_degree, count,
-                                                                    ws.visited, ws.f0, ws.f1, a.reach, a.dsum,
-                                                                    ws.harm, ws.ctrl);
-                return grx_frontier_advance(ws.ctrl, st);
-            });
+        const int rc = ms_bfs<W>("grx_distance_sums: the BFS did not end after %lld levels", a, ws, a.sources + first,
+                                 count, cl_sums<W>{reach, dsum, ws.harm}, st);
         if (rc != GRX_OK) return rc;
     }
-    cl_harmonic_kernel<<<grx_grid(n, CL_BLOCK, CL_MAX_BLOCKS), CL_BLOCK, 0, st>>>(n, ws.harm, a.harmonic);
+    cl_harmonic_kernel<<<grx_grid(a.n, CL_BLOCK, CL_MAX_BLOCKS), CL_BLOCK, 0, st>>>(a.n, ws.harm, harmonic);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }
 
 // ---- eccentricities (grx_eccentricity) ---------------------------------------------------------------------------
-// The same bitset BFS with an extremal reduction in place of the sums.  Pass A of a batch: reach(v) += c,
+// The level core with an extremal reduction in place of the sums, as two bodies.  Pass A of a batch: reach(v) += c,
 // lower(v) = max(lower(v), d) for the level d at which new source bits arrive at v, and ecc(b) = the last level at which
 // bit b was newly set anywhere (every workgroup ORs its `next` words through LDS and one lane per set bit stores d into
 // the batch's int32 slots: many workgroups store the same value in one launch, plain stores).  Pass B, with the upper
@@ -318,25 +374,6 @@ int run(const Args &a, const ClWs &ws, hipStream_t st)
 // valid where d(s, v) = d(v, s): a symmetric CSR.  A source's own level-0 update pins lower = upper = ecc there.
 
 constexpr int EC_WAVES = CL_BLOCK / GRX_WAVE;
-
-size_t ec_ws_bytes(int64_t n, int W)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    return 3 * grx_align_up(nn * (size_t)W * 8, 256) + 256;
-}
-
-ClWs ec_carve(void *base, int64_t n, int W)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    char *p = reinterpret_cast<char *>(base);
-    ClWs ws;
-    ws.visited = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
-    ws.f0 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
-    ws.f1 = reinterpret_cast<uint64_t *>(p); p += grx_align_up(nn * (size_t)W * 8, 256);
-    ws.harm = nullptr;
-    ws.ctrl = reinterpret_cast<int32_t *>(p);
-    return ws;
-}
 
 // min resp. max over the W lanes of a group (every lane of the wavefront takes part)
 template <int W>
@@ -376,193 +413,96 @@ __global__ __launch_bounds__(CL_BLOCK) void ec_source_bounds_kernel(int64_t n, i
     }
 }
 
-// one level, rows up to hub_degree arcs (the shape of cl_level_kernel).  secc: the batch's int32[count] slots of the
-// source eccentricities, written by pass A (BOUNDS = false) and read by pass B
-template <int W, bool BOUNDS>
-__global__ __launch_bounds__(CL_BLOCK) void ec_level_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
-                                                            const int32_t *__restrict__ col, int64_t hub_degree,
-                                                            int count, uint64_t *__restrict__ visited,
-                                                            uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
-                                                            int32_t *__restrict__ secc, int64_t *__restrict__ reach,
-                                                            int32_t *__restrict__ lower, int32_t *__restrict__ upper,
-                                                            int32_t *__restrict__ ctrl)
-{
-    constexpr int GROUPS = CL_BLOCK / W;
-    __shared__ int32_t ecc[BOUNDS ? GRX_WAVE * W : 1];
-    __shared__ uint64_t seen_of[BOUNDS ? 1 : EC_WAVES][W];
-    if (ctrl[GRX_CT_DONE]) return;                          // the same in every lane of the launch
-    const int l = ctrl[GRX_CT_LEVEL], d = l + 1;
-    const uint64_t *F = (l & 1) ? f1 : f0;
-    uint64_t *Fn = (l & 1) ? f0 : f1;
-    const int w = threadIdx.x % W;
-    const uint64_t active = active_mask(count, w);
-    if constexpr (BOUNDS) {
-        for (int b = threadIdx.x; b < GRX_WAVE * W; b += CL_BLOCK) ecc[b] = b < count ? secc[b] : 0;
-        __syncthreads();
+// pass A.  secc: the batch's int32[count] slots of the source eccentricities, written here and read by pass B
+template <int W>
+struct ec_reach {
+    int32_t *__restrict__ secc;
+    int64_t *__restrict__ reach;
+    int32_t *__restrict__ lower;
+    struct Shared { uint64_t seen_of[EC_WAVES][W]; };
+    struct Acc { uint64_t seen; };                           // word w of every new bit of the thread's nodes
+    struct View {};
+    __device__ __forceinline__ View row_begin(Shared &, int) const { return {}; }
+    __device__ __forceinline__ View hub_begin(const uint64_t *part, int d) const
+    {
+        for (int b = threadIdx.x; b < GRX_WAVE * W; b += CL_BLOCK)
+            if ((part[b / GRX_WAVE] >> (b % GRX_WAVE)) & 1) secc[b] = d;
+        return {};
     }
-    int found = 0;
-    uint64_t seen = 0;
-    // the trip count is the same in every lane of the workgroup: the group reductions below see every lane
-    for (int64_t first = (int64_t)blockIdx.x * GROUPS; first < n; first += (int64_t)gridDim.x * GROUPS) {
-        const int64_t v = first + threadIdx.x / W;
-        bool mine = false;
-        uint64_t nw = 0;
-        if (v < n) {
-            const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-            if (e - b <= hub_degree) {                      // longer rows: ec_level_hub_kernel
-                mine = true;
-                const int64_t cell = v * W + w;
-                const uint64_t vw = visited[cell];
-                nw = pull_words<W>(b, e, 1, col, F, w, active & ~vw);
-                Fn[cell] = nw;
-                if (nw) visited[cell] = vw | nw;
-            }
-        }
-        if constexpr (BOUNDS) {
-            int lo, hi;
-            ecc_range(nw, ecc + w * GRX_WAVE, lo, hi);
-            group_min_max<W>(lo, hi);
-            if (mine && w == 0 && hi >= 0) {
-                upper[v] = min(upper[v], d + lo);
-                lower[v] = max(lower[v], hi - d);
-                found = 1;
-            }
-        } else {
-            seen |= nw;
-            const int c = group_sum<W>(__popcll(nw));
-            if (mine && w == 0 && c) {
-                reach[v] += c;
-                lower[v] = max(lower[v], d);
-                found = 1;
-            }
-        }
+    __device__ __forceinline__ bool node(int64_t v, uint64_t nw, bool writer, int d, int, View, Acc &a) const
+    {
+        a.seen |= nw;
+        const int c = group_sum<W>(__popcll(nw));
+        if (!(writer && c)) return false;
+        const int64_t r = reach[v];                         // both loads before the stores: __restrict__ on a member
+        const int32_t lw = lower[v];                        // does not let the compiler move the second one up
+        reach[v] = r + c;
+        lower[v] = max(lw, d);
+        return true;
     }
-    if (__ballot(found != 0) && threadIdx.x % GRX_WAVE == 0) ctrl[GRX_CT_FOUND] = 1;
-    if constexpr (!BOUNDS) {
+    __device__ __forceinline__ void row_end(Shared &sh, const Acc &a, int d, int w) const
+    {
         // OR over the lanes of the wavefront that hold word w, then over the wavefronts through LDS
+        uint64_t seen = a.seen;
 #pragma unroll
         for (int off = W; off < GRX_WAVE; off <<= 1)
             seen |= __shfl_xor((unsigned long long)seen, off, GRX_WAVE);
-        if (threadIdx.x % GRX_WAVE < W) seen_of[threadIdx.x / GRX_WAVE][w] = seen;
+        if (threadIdx.x % GRX_WAVE < W) sh.seen_of[threadIdx.x / GRX_WAVE][w] = seen;
         __syncthreads();
         for (int b = threadIdx.x; b < GRX_WAVE * W; b += CL_BLOCK) {
             uint64_t m = 0;
 #pragma unroll
-            for (int k = 0; k < EC_WAVES; ++k) m |= seen_of[k][b / GRX_WAVE];
+            for (int k = 0; k < EC_WAVES; ++k) m |= sh.seen_of[k][b / GRX_WAVE];
             if ((m >> (b % GRX_WAVE)) & 1) secc[b] = d;     // set bits lie below `count`
         }
     }
-}
-
-// one level, hub rows (the shape of cl_level_hub_kernel)
-template <int W, bool BOUNDS>
-__global__ __launch_bounds__(CL_BLOCK) void ec_level_hub_kernel(const int64_t *__restrict__ row_ptr,
-                                                                const int32_t *__restrict__ col,
-                                                                const int32_t *__restrict__ hub_rows, int count,
-                                                                uint64_t *__restrict__ visited,
-                                                                uint64_t *__restrict__ f0, uint64_t *__restrict__ f1,
-                                                                int32_t *__restrict__ secc,
-                                                                int64_t *__restrict__ reach,
-                                                                int32_t *__restrict__ lower,
-                                                                int32_t *__restrict__ upper,
-                                                                int32_t *__restrict__ ctrl)
-{
-    constexpr int GROUPS = CL_BLOCK / W;
-    __shared__ uint64_t part[CL_BLOCK];
-    if (ctrl[GRX_CT_DONE]) return;
-    const int l = ctrl[GRX_CT_LEVEL], d = l + 1;
-    const uint64_t *F = (l & 1) ? f1 : f0;
-    uint64_t *Fn = (l & 1) ? f0 : f1;
-    const int t = threadIdx.x, w = t % W;
-    const int64_t v = hub_rows[blockIdx.x];
-    const int64_t cell = v * W + w;
-    const uint64_t vw = visited[cell];
-    part[t] = pull_words<W>(row_ptr[v] + t / W, row_ptr[v + 1], GROUPS, col, F, w, active_mask(count, w) & ~vw);
-    __syncthreads();
-#pragma unroll
-    for (int s = CL_BLOCK / 2; s >= W; s >>= 1) {          // part[t] for t < W: the OR over every group
-        if (t < s) part[t] |= part[t + s];
-        __syncthreads();
-    }
-    if constexpr (!BOUNDS) {
-        for (int b = t; b < GRX_WAVE * W; b += CL_BLOCK)
-            if ((part[b / GRX_WAVE] >> (b % GRX_WAVE)) & 1) secc[b] = d;
-    }
-    if (t >= GRX_WAVE) return;
-    const uint64_t nw = t < W ? part[t] : 0;
-    if (t < W) {
-        Fn[cell] = nw;
-        if (nw) visited[cell] = vw | nw;
-    }
-    if constexpr (BOUNDS) {
-        int lo, hi;
-        ecc_range(nw, secc + w * GRX_WAVE, lo, hi);         // a few rows: straight from global memory
-        group_min_max<W>(lo, hi);
-        if (t == 0 && hi >= 0) {
-            upper[v] = min(upper[v], d + lo);
-            lower[v] = max(lower[v], hi - d);
-            ctrl[GRX_CT_FOUND] = 1;
-        }
-    } else {
-        const int c = group_sum<W>(__popcll(nw));
-        if (t == 0 && c) {
-            reach[v] += c;
-            lower[v] = max(lower[v], d);
-            ctrl[GRX_CT_FOUND] = 1;
-        }
-    }
-}
-
-struct EcArgs {
-    int64_t n;
-    const int64_t *row_ptr;
-    const int32_t *col;
-    const int32_t *hub_rows;
-    int64_t n_hub_rows, hub_degree;
-    const int32_t *sources;
-    int64_t n_sources;
-    int32_t *source_ecc;
-    int64_t *reach;
-    int32_t *lower, *upper;
 };
 
-// one BFS of the batch [first, first + count): pass A, or pass B over the same sources
-template <int W, bool BOUNDS>
-int ec_bfs(const EcArgs &a, const ClWs &ws, int64_t first, int count, hipStream_t st)
-{
-    const int64_t n = a.n;
-    const unsigned row_blocks = grx_grid(n, CL_BLOCK / W, CL_MAX_ROW_BLOCKS);
-    int32_t *secc = a.source_ecc + first;
-    grx_fill64(ws.visited, n * W, 0, st);
-    grx_fill64(ws.f0, n * W, 0, st);
-    cl_source_init_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
-        n, W, count, a.sources + first, ws.visited, ws.f0, ws.ctrl);
-    if (BOUNDS)
-        ec_source_bounds_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(
-            n, count, a.sources + first, secc, a.lower, a.upper);
-    GRX_LAUNCH_CHECK();
-    int32_t h[2];
-    // a BFS has at most n - 1 levels; one more launch finds the empty frontier
-    return grx_run_rounds(
-        "grx_eccentricity: the BFS did not end after %lld levels", CL_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
-            if (a.n_hub_rows)
-                ec_level_hub_kernel<W, BOUNDS><<<(unsigned)a.n_hub_rows, CL_BLOCK, 0, st>>>(
-                    a.row_ptr, a.col, a.hub_rows, count, ws.visited, ws.f0, ws.f1, secc, a.reach, a.lower, a.upper,
-                    ws.ctrl);
-            ec_level_kernel<W, BOUNDS><<<row_blocks, CL_BLOCK, 0, st>>>(n, a.row_ptr, a.col, a.hub_degree, count,
-                                                                        ws.visited, ws.f0, ws.f1, secc, a.reach,
-                                                                        a.lower, a.upper, ws.ctrl);
-            return grx_frontier_advance(ws.ctrl, st);
-        });
-}
-
+// pass B: ecc(b) staged in LDS for the row kernel, and straight from global memory for the few hub rows
 template <int W>
-int ec_run(const EcArgs &a, const ClWs &ws, hipStream_t st)
+struct ec_bounds {
+    const int32_t *__restrict__ secc;
+    int32_t *__restrict__ lower, *__restrict__ upper;
+    struct Shared { int32_t ecc[GRX_WAVE * W]; };
+    struct Acc {};
+    typedef const int32_t *View;                             // where node() reads ecc(b)
+    __device__ __forceinline__ View row_begin(Shared &sh, int count) const
+    {
+        for (int b = threadIdx.x; b < GRX_WAVE * W; b += CL_BLOCK) sh.ecc[b] = b < count ? secc[b] : 0;
+        __syncthreads();
+        return sh.ecc;
+    }
+    __device__ __forceinline__ View hub_begin(const uint64_t *, int) const { return secc; }
+    __device__ __forceinline__ bool node(int64_t v, uint64_t nw, bool writer, int d, int w, View ecc, Acc &) const
+    {
+        int lo, hi;
+        ecc_range(nw, ecc + w * GRX_WAVE, lo, hi);
+        group_min_max<W>(lo, hi);
+        if (!(writer && hi >= 0)) return false;
+        const int32_t up = upper[v], lw = lower[v];         // both loads before the stores, as in ec_reach
+        upper[v] = min(up, d + lo);
+        lower[v] = max(lw, hi - d);
+        return true;
+    }
+    __device__ __forceinline__ void row_end(Shared &, const Acc &, int, int) const {}
+};
+
+// per batch: pass A, then pass B over the same sources when the upper bounds are asked for
+template <int W>
+int ec_run(const MsArgs &a, const MsWs &ws, int32_t *source_ecc, int64_t *reach, int32_t *lower, int32_t *upper,
+           hipStream_t st)
 {
+    const char *what = "grx_eccentricity: the BFS did not end after %lld levels";
     for (int64_t first = 0; first < a.n_sources; first += 64 * W) {
         const int count = (int)std::min<int64_t>(64 * W, a.n_sources - first);
-        int rc = ec_bfs<W, false>(a, ws, first, count, st);
-        if (rc == GRX_OK && a.upper) rc = ec_bfs<W, true>(a, ws, first, count, st);
+        const int32_t *src = a.sources + first;
+        int32_t *secc = source_ecc + first;
+        int rc = ms_bfs<W>(what, a, ws, src, count, ec_reach<W>{secc, reach, lower}, st);
+        if (rc == GRX_OK && upper) {
+            ec_source_bounds_kernel<<<(unsigned)grx_ceil_div(count, CL_BLOCK), CL_BLOCK, 0, st>>>(a.n, count, src,
+                                                                                                  secc, lower, upper);
+            rc = ms_bfs<W>(what, a, ws, src, count, ec_bounds<W>{secc, lower, upper}, st);
+        }
         if (rc != GRX_OK) return rc;
     }
     return GRX_OK;
@@ -574,7 +514,7 @@ extern "C" {
 
 size_t grx_distance_sums_workspace_bytes(int64_t n, int words, int64_t n_sources)
 {
-    return ws_bytes(n, choose_words(n, words, n_sources));
+    return ws_bytes(n, choose_words(n, words, n_sources), true);
 }
 
 int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
@@ -592,28 +532,24 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
     GRX_REQUIRE(lanes_per_row >= 1, "grx_distance_sums: lanes_per_row must be >= 1");
     GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows), "grx_distance_sums: hub list");
     const int W = choose_words(n, words, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, W), "grx_distance_sums: workspace %zu bytes, need %zu",
-                workspace_bytes, ws_bytes(n, W));
+    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, W, true), "grx_distance_sums: workspace %zu bytes, need %zu",
+                workspace_bytes, ws_bytes(n, W, true));
     hipStream_t st = grx_stream(stream);
-    const ClWs ws = carve(d_workspace, n, W);
-    const Args a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
-                 d_sources, n_sources, d_reach, d_dsum, d_harmonic};
+    const MsWs ws = carve(d_workspace, n, W, true);
+    const MsArgs a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
+                   d_sources, n_sources};
     grx_fill64(reinterpret_cast<uint64_t *>(d_reach), n, 0, st);
     grx_fill64(reinterpret_cast<uint64_t *>(d_dsum), n, 0, st);
     grx_fill64(ws.harm, 2 * n, 0, st);
     GRX_LAUNCH_CHECK();
-    switch (W) {
-    case 1: return run<1>(a, ws, st);
-    case 2: return run<2>(a, ws, st);
-    case 4: return run<4>(a, ws, st);
-    case 8: return run<8>(a, ws, st);
-    default: return run<16>(a, ws, st);
-    }
+    return ms_with_words(W, [&](auto words) {
+        return sums_run<decltype(words)::value>(a, ws, d_reach, d_dsum, d_harmonic, st);
+    });
 }
 
 size_t grx_eccentricity_workspace_bytes(int64_t n, int words, int64_t n_sources)
 {
-    return ec_ws_bytes(n, choose_words(n, words, n_sources));
+    return ws_bytes(n, choose_words(n, words, n_sources), false);
 }
 
 int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
@@ -632,12 +568,12 @@ int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
     GRX_REQUIRE(accumulate == 0 || accumulate == 1, "grx_eccentricity: accumulate must be 0 or 1 (got %d)",
                 accumulate);
     const int W = choose_words(n, words, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ec_ws_bytes(n, W), "grx_eccentricity: workspace %zu bytes, need %zu",
-                workspace_bytes, ec_ws_bytes(n, W));
+    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, W, false), "grx_eccentricity: workspace %zu bytes, need %zu",
+                workspace_bytes, ws_bytes(n, W, false));
     hipStream_t st = grx_stream(stream);
-    const ClWs ws = ec_carve(d_workspace, n, W);
-    const EcArgs a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
-                   d_sources, n_sources, d_source_ecc, d_reach, d_lower, d_upper};
+    const MsWs ws = carve(d_workspace, n, W, false);
+    const MsArgs a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
+                   d_sources, n_sources};
     if (!accumulate) {
         grx_fill64(reinterpret_cast<uint64_t *>(d_reach), n, 0, st);
         grx_fill32(d_lower, n, 0, st);
@@ -645,13 +581,9 @@ int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
     }
     if (n_sources) grx_fill32(d_source_ecc, n_sources, 0, st);
     GRX_LAUNCH_CHECK();
-    switch (W) {
-    case 1: return ec_run<1>(a, ws, st);
-    case 2: return ec_run<2>(a, ws, st);
-    case 4: return ec_run<4>(a, ws, st);
-    case 8: return ec_run<8>(a, ws, st);
-    default: return ec_run<16>(a, ws, st);
-    }
+    return ms_with_words(W, [&](auto words) {
+        return ec_run<decltype(words)::value>(a, ws, d_source_ecc, d_reach, d_lower, d_upper, st);
+    });
 }
 
 }  // extern "C"

@@ -88,14 +88,14 @@ void grx_fill64(uint64_t *d_dst, int64_t count, uint64_t value, hipStream_t st);
 // ---- round loops the device steers (BFS levels, peeling rounds, power iterations) -------------------------------
 // A loop whose trip count only the device knows keeps a few int32 control words at the end of its workspace.  In every
 // layout word 0 is `done` and word 1 the counter (BFS level, peeling layer, iteration count); the BFS loops share the
-// three words below, and a file with more words continues its own enum after them (grx_kcore.hip's KT_* and
+// three words below, and a file with more words continues its own enum after them (grx_peel.h's PL_* and
 // grx_measures.hip's CT_ITERS name words 0 and 1 their own way).  Every kernel of a round returns at once when `done`
 // is set, and a one-thread kernel at the end of the round advances the counter or sets `done`.  So the host enqueues
 // a fixed batch of rounds without waiting, reads the control words back once per batch (grx_read_ctrl: grx_fetch_begin
 // + grx_fetch_wait into one pinned block per host thread, allocated on first use and freed when the thread ends) and
 // repeats until `done`: the results are those of a loop that checked after every round.
 enum { GRX_CT_DONE = 0, GRX_CT_LEVEL, GRX_CT_FOUND, GRX_CT_BFS_WORDS };
-constexpr int GRX_CTRL_MAX_WORDS = 16;   // the pinned block; the widest user has 8 (grx_kcore.hip)
+constexpr int GRX_CTRL_MAX_WORDS = 16;   // the pinned block; the widest user has 9 (grx_peel.h)
 
 // out[0 .. words) = d_ctrl[0 .. words) once everything queued on st has finished
 int grx_read_ctrl(const int32_t *d_ctrl, int words, int32_t *out, hipStream_t st);

@@ -11,13 +11,10 @@
 //       for v in F, for every arc between v and a node u: deg(u) -= 1
 //       layer += 1
 //
-// The frontier is a list, not a scan.  A node that is alive and outside F at the start of a round has deg > k, so the
-// F of the next round is exactly the set of nodes some decrement of this round takes from above k to k or below, and
-// of all the decrements a node receives exactly one does that (integer atomicSub returns the value before).  The thread
-// that sees old > k >= old - c appends the node to the next round's list and writes its core, onion layer and state
-// there and then.  Only when that list comes out empty (k must jump) do two sweeps over all n nodes run: kc_min (the
-// chip-wide minimum degree of the alive nodes: a wavefront reduction, one integer atomicMin per workgroup) and
-// kc_collect (F by the new k, appended one atomic per wavefront).
+// The peeling itself -- the frontier list, the crossing decrement, the LDS append buffer, the two sweeps of a round
+// whose list came out empty (k must jump) and the one-thread finalize -- is grx_peel.h with nodes for items, deg for
+// the value, k for the threshold and the onion layer for the round.  The thread that sees old > k >= old - c writes the
+// node's core, onion layer and state there and then.
 // Bound: 2 (distinct core values) sweeps of 8 n bytes, plus one visit of every arc from each of its ends over the
 // whole run (a 4-byte gather of the other end's state; an atomicSub only when that end is still alive: about one per
 // edge), plus the hub pulls below.  Never rounds x n.
@@ -37,26 +34,18 @@
 //
 // State word of a node: > 0 = the round it left in (its onion layer); <= 0 = alive, minus the hub bits (1 = listed in
 // the out CSR's hub list, 2 = in the in CSR's; both for an undirected graph).  A decrement that reaches a node after
-// its crossing decrement (or after it left) changes nothing that is read again.  Appends go through an LDS buffer per
-// workgroup: one global atomic per workgroup and round on the list counter.
-// A one-thread finalize subtracts |F| from the alive count, advances `layer` or sets `done`, and raises the sweep flag
-// when the next list is empty; the rounds run as a device-steered round loop (grx_common.h).  Integer arithmetic only;
-// core and onion are the same in every run (the order of the lists is not, and is never visible).  The CSRs must hold
-// no self-loop (the caller's precondition).
-#include "grx_common.h"
-
-#include <climits>
+// its crossing decrement (or after it left) changes nothing that is read again.
+// Integer arithmetic only; core and onion are the same in every run (the order of the lists is not, and is never
+// visible).  The CSRs must hold no self-loop (the caller's precondition).
+#include "grx_peel.h"
 
 namespace {
 
-constexpr int KC_BLOCK = 256;
+constexpr int KC_BLOCK = PL_BLOCK;                           // the appending kernels flush with pl_flush
 constexpr int KC_GROUP = 8;                                  // lanes per frontier node in kc_peel_kernel
 constexpr int KC_ROUND_BATCH = 16;                           // rounds enqueued between two read-backs
-constexpr int KC_MAX_BLOCKS = 2048;
-constexpr int KC_APPEND_CAP = 2048;                          // LDS append buffer of a workgroup (entries)
+constexpr int KC_MAX_BLOCKS = 2048;                          // workgroups of kc_init and kc_peel
 constexpr int KC_OUT_HUB = 1, KC_IN_HUB = 2;
-
-enum { KT_DONE = 0, KT_LAYER, KT_K, KT_MIN, KT_SWEEP, KT_ALIVE, KT_CNT0, KT_CNT1, KT_WORDS };
 
 size_t ws_bytes(int64_t n)
 {
@@ -64,10 +53,19 @@ size_t ws_bytes(int64_t n)
     return 4 * grx_align_up(nn * 4, 256) + 256;
 }
 
+// the workspace, the outputs, and the items of grx_peel.h: a node, alive while its state word is <= 0, valued by deg
 struct KcState {
-    int32_t *deg, *state, *list0, *list1;
-    int32_t *ctrl;
+    int32_t *deg, *state;
+    PlLists pl;
     int64_t *core, *onion;                                   // onion may be null
+    __device__ __forceinline__ bool alive(int64_t v) const { return state[v] <= 0; }
+    __device__ __forceinline__ int value(int64_t v) const { return deg[v]; }
+    __device__ __forceinline__ void leave(int64_t v, int layer, int k) const
+    {
+        state[v] = layer;
+        core[v] = k;
+        if (onion) onion[v] = layer;
+    }
 };
 
 KcState carve(void *base, int64_t n, int64_t *core, int64_t *onion)
@@ -77,66 +75,31 @@ KcState carve(void *base, int64_t n, int64_t *core, int64_t *onion)
     KcState s;
     s.deg = reinterpret_cast<int32_t *>(p); p += step;
     s.state = reinterpret_cast<int32_t *>(p); p += step;
-    s.list0 = reinterpret_cast<int32_t *>(p); p += step;
-    s.list1 = reinterpret_cast<int32_t *>(p); p += step;
-    s.ctrl = reinterpret_cast<int32_t *>(p);
+    s.pl.list0 = reinterpret_cast<int32_t *>(p); p += step;
+    s.pl.list1 = reinterpret_cast<int32_t *>(p); p += step;
+    s.pl.ctrl = reinterpret_cast<int32_t *>(p);
     s.core = core;
     s.onion = onion;
     return s;
 }
 
-// what a round's kernels read from ctrl: the list of this round (F) and the one they append to
-struct KcRound {
-    int layer, kk, count;
-    const int32_t *cur;
-    int32_t *next, *next_count;
-};
-
-__device__ __forceinline__ KcRound round_of(const KcState &s)
-{
-    KcRound r;
-    r.layer = s.ctrl[KT_LAYER];
-    r.kk = s.ctrl[KT_SWEEP] ? max(s.ctrl[KT_K], s.ctrl[KT_MIN]) : s.ctrl[KT_K];
-    const int odd = r.layer & 1;
-    r.count = s.ctrl[KT_CNT0 + odd];
-    r.cur = odd ? s.list1 : s.list0;
-    r.next = odd ? s.list0 : s.list1;
-    r.next_count = &s.ctrl[KT_CNT0 + (odd ^ 1)];
-    return r;
-}
-
 // deg(u) -= c; the one decrement that takes u from above k to k or below puts u into the next round's F
-__device__ __forceinline__ void drop(int32_t u, int c, const KcRound &r, const KcState &s, int32_t *buf, int *bcount)
+__device__ __forceinline__ void drop(int32_t u, int c, const PlRound &r, const KcState &s, PlAppends &ap)
 {
     const int old = atomicSub(&s.deg[u], c);
-    if (old > r.kk && old - c <= r.kk) {
-        s.state[u] = r.layer + 1;
-        s.core[u] = r.kk;
-        if (s.onion) s.onion[u] = r.layer + 1;
-        const int slot = atomicAdd(bcount, 1);
-        if (slot < KC_APPEND_CAP) buf[slot] = u;
-        else r.next[atomicAdd(r.next_count, 1)] = u;
+    if (pl_crosses(old, c, r.thr)) {
+        s.leave(u, r.round + 1, r.thr);
+        pl_append(u, r, ap);
     }
 }
 
 // a node of F tells the other end u of one arc -- unless u left in this or an earlier round, or is an alive hub of
 // the CSR that holds the arc on u's side (`skip`: u's workgroup pulls it)
-__device__ __forceinline__ void push_arc(int32_t u, int skip, const KcRound &r, const KcState &s, int32_t *buf,
-                                         int *bcount)
+__device__ __forceinline__ void push_arc(int32_t u, int skip, const PlRound &r, const KcState &s, PlAppends &ap)
 {
     const int32_t su = s.state[u];
-    if (su > 0 ? su <= r.layer : ((-su) & skip) != 0) return;
-    drop(u, 1, r, s, buf, bcount);
-}
-
-// the workgroup's buffered appends, one atomic on the list counter; every thread of the workgroup calls it
-__device__ __forceinline__ void flush_appends(const KcRound &r, const int32_t *buf, const int *bcount, int *base)
-{
-    __syncthreads();
-    const int c = min(*bcount, KC_APPEND_CAP);
-    if (threadIdx.x == 0 && c) *base = atomicAdd(r.next_count, c);
-    __syncthreads();
-    for (int i = threadIdx.x; i < c; i += KC_BLOCK) r.next[*base + i] = buf[i];
+    if (su > 0 ? su <= r.round : ((-su) & skip) != 0) return;
+    drop(u, 1, r, s, ap);
 }
 
 __global__ __launch_bounds__(KC_BLOCK) void kc_init_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
@@ -148,10 +111,7 @@ __global__ __launch_bounds__(KC_BLOCK) void kc_init_kernel(int64_t n, const int6
         s.deg[v] = (int32_t)d;
         s.state[v] = 0;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        s.ctrl[KT_DONE] = 0; s.ctrl[KT_LAYER] = 1; s.ctrl[KT_K] = 0; s.ctrl[KT_MIN] = INT_MAX;
-        s.ctrl[KT_SWEEP] = 1; s.ctrl[KT_ALIVE] = (int32_t)n; s.ctrl[KT_CNT0] = 0; s.ctrl[KT_CNT1] = 0;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) pl_init_ctrl(s.pl.ctrl, (int32_t)n);
 }
 
 // the hub bits of the state words (every listed row once per list: no two threads of a launch share a word)
@@ -165,50 +125,6 @@ __global__ __launch_bounds__(KC_BLOCK) void kc_hub_flag_kernel(int64_t n, const 
     state[h] = -((-state[h]) | bits);
 }
 
-// sweep 1 (only when the list is empty): min deg over the alive nodes
-__global__ __launch_bounds__(KC_BLOCK) void kc_min_kernel(int64_t n, KcState s)
-{
-    __shared__ int smin;
-    if (s.ctrl[KT_DONE] || !s.ctrl[KT_SWEEP]) return;
-    if (threadIdx.x == 0) smin = INT_MAX;
-    __syncthreads();
-    int m = INT_MAX;
-    for (int64_t v = (int64_t)blockIdx.x * KC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * KC_BLOCK)
-        if (s.state[v] <= 0) m = min(m, s.deg[v]);
-#pragma unroll
-    for (int off = GRX_WAVE / 2; off > 0; off >>= 1) m = min(m, __shfl_xor(m, off, GRX_WAVE));
-    if (threadIdx.x % GRX_WAVE == 0 && m < INT_MAX) atomicMin(&smin, m);
-    __syncthreads();
-    if (threadIdx.x == 0 && smin < INT_MAX) atomicMin(&s.ctrl[KT_MIN], smin);
-}
-
-// sweep 2: F = the alive nodes with deg <= max(k, min), appended one atomic per wavefront
-__global__ __launch_bounds__(KC_BLOCK) void kc_collect_kernel(int64_t n, KcState s)
-{
-    if (s.ctrl[KT_DONE] || !s.ctrl[KT_SWEEP]) return;
-    const int layer = s.ctrl[KT_LAYER];
-    const int kk = max(s.ctrl[KT_K], s.ctrl[KT_MIN]);
-    int32_t *cur = (layer & 1) ? s.list1 : s.list0;
-    int32_t *cur_count = &s.ctrl[KT_CNT0 + (layer & 1)];
-    const int lane = threadIdx.x % GRX_WAVE;
-    // the trip count is the same in every lane of the workgroup: the ballot sees every lane
-    for (int64_t first = (int64_t)blockIdx.x * KC_BLOCK; first < n; first += (int64_t)gridDim.x * KC_BLOCK) {
-        const int64_t v = first + threadIdx.x;
-        const bool leaves = v < n && s.state[v] <= 0 && s.deg[v] <= kk;
-        const unsigned long long m = __ballot(leaves);
-        if (!m) continue;
-        int base = 0;
-        if (lane == 0) base = atomicAdd(cur_count, __popcll(m));
-        base = __shfl(base, 0, GRX_WAVE);
-        if (leaves) {
-            cur[base + __popcll(m & ((1ull << lane) - 1))] = (int32_t)v;
-            s.state[v] = layer;
-            s.core[v] = kk;
-            if (s.onion) s.onion[v] = layer;
-        }
-    }
-}
-
 // the peel of the rows up to hub_degree arcs: KC_GROUP lanes per node of F, over the list
 __global__ __launch_bounds__(KC_BLOCK) void kc_peel_kernel(const int64_t *__restrict__ row_ptr,
                                                            const int32_t *__restrict__ col, int64_t hub_degree,
@@ -216,11 +132,10 @@ __global__ __launch_bounds__(KC_BLOCK) void kc_peel_kernel(const int64_t *__rest
                                                            const int32_t *__restrict__ in_col, int64_t in_hub_degree,
                                                            KcState s)
 {
-    __shared__ int32_t buf[KC_APPEND_CAP];
-    __shared__ int bcount, base;
-    if (s.ctrl[KT_DONE]) return;
-    const KcRound r = round_of(s);
-    if (threadIdx.x == 0) bcount = 0;
+    __shared__ PlAppends ap;
+    if (s.pl.ctrl[PL_DONE]) return;
+    const PlRound r = round_of(s.pl);
+    if (threadIdx.x == 0) ap.count = 0;
     __syncthreads();
     constexpr int NODES = KC_BLOCK / KC_GROUP;
     const int g = threadIdx.x % KC_GROUP;
@@ -229,14 +144,14 @@ __global__ __launch_bounds__(KC_BLOCK) void kc_peel_kernel(const int64_t *__rest
         const int64_t v = r.cur[i];
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
         if (e - b <= hub_degree)                              // longer rows: kc_hub_kernel
-            for (int64_t j = b + g; j < e; j += KC_GROUP) push_arc(col[j], KC_IN_HUB, r, s, buf, &bcount);
+            for (int64_t j = b + g; j < e; j += KC_GROUP) push_arc(col[j], KC_IN_HUB, r, s, ap);
         if (in_row_ptr) {
             const int64_t ib = in_row_ptr[v], ie = in_row_ptr[v + 1];
             if (ie - ib <= in_hub_degree)
-                for (int64_t j = ib + g; j < ie; j += KC_GROUP) push_arc(in_col[j], KC_OUT_HUB, r, s, buf, &bcount);
+                for (int64_t j = ib + g; j < ie; j += KC_GROUP) push_arc(in_col[j], KC_OUT_HUB, r, s, ap);
         }
     }
-    flush_appends(r, buf, &bcount, &base);
+    pl_flush(r, ap);
 }
 
 // one workgroup per hub row of one CSR: a hub in F pushes along its row; a hub that stays alive pulls -- counts the
@@ -246,47 +161,29 @@ __global__ __launch_bounds__(KC_BLOCK) void kc_hub_kernel(int64_t n, const int64
                                                           const int32_t *__restrict__ col,
                                                           const int32_t *__restrict__ hub_rows, int skip, KcState s)
 {
-    __shared__ int32_t buf[KC_APPEND_CAP];
-    __shared__ int bcount, base, total, own;
-    if (s.ctrl[KT_DONE]) return;
-    const KcRound r = round_of(s);
+    __shared__ PlAppends ap;
+    __shared__ int total, own;
+    if (s.pl.ctrl[PL_DONE]) return;
+    const PlRound r = round_of(s.pl);
     const int t = threadIdx.x;
     const int32_t v = hub_rows[blockIdx.x];
     if (v < 0 || v >= n) return;                             // an id outside [0, n) is never read through
-    if (t == 0) { bcount = 0; total = 0; own = s.state[v]; }   // one read: every wavefront takes the same branch
+    if (t == 0) { ap.count = 0; total = 0; own = s.state[v]; }   // one read: every wavefront takes the same branch
     __syncthreads();
     const int sv = own;
     const int64_t b = row_ptr[v], e = row_ptr[v + 1];
-    if (sv == r.layer) {
-        for (int64_t j = b + t; j < e; j += KC_BLOCK) push_arc(col[j], skip, r, s, buf, &bcount);
+    if (sv == r.round) {
+        for (int64_t j = b + t; j < e; j += KC_BLOCK) push_arc(col[j], skip, r, s, ap);
     } else if (sv <= 0) {
         int c = 0;
-        for (int64_t j = b + t; j < e; j += KC_BLOCK) c += s.state[col[j]] == r.layer;
+        for (int64_t j = b + t; j < e; j += KC_BLOCK) c += s.state[col[j]] == r.round;
 #pragma unroll
         for (int off = GRX_WAVE / 2; off > 0; off >>= 1) c += __shfl_xor(c, off, GRX_WAVE);
         if (t % GRX_WAVE == 0 && c) atomicAdd(&total, c);
         __syncthreads();
-        if (t == 0 && total) drop(v, total, r, s, buf, &bcount);
+        if (t == 0 && total) drop(v, total, r, s, ap);
     }
-    flush_appends(r, buf, &bcount, &base);
-}
-
-// one thread: F has left; the next round, or done when nobody is alive.  An empty next list asks for the sweeps
-__global__ void kc_finalize_kernel(KcState s)
-{
-    int32_t *ctrl = s.ctrl;
-    if (ctrl[KT_DONE]) return;
-    const int odd = ctrl[KT_LAYER] & 1;
-    if (ctrl[KT_SWEEP]) ctrl[KT_K] = max(ctrl[KT_K], ctrl[KT_MIN]);
-    ctrl[KT_ALIVE] -= ctrl[KT_CNT0 + odd];
-    ctrl[KT_CNT0 + odd] = 0;
-    ctrl[KT_MIN] = INT_MAX;
-    if (ctrl[KT_ALIVE] <= 0) {
-        ctrl[KT_DONE] = 1;                                  // KT_LAYER stays: the number of rounds run
-        return;
-    }
-    ctrl[KT_SWEEP] = ctrl[KT_CNT0 + (odd ^ 1)] == 0;
-    ctrl[KT_LAYER] += 1;
+    pl_flush(r, ap);
 }
 
 }  // namespace
@@ -320,10 +217,10 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
     const KcState s = carve(d_workspace, n, d_core, d_onion);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
     const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
-    const unsigned sweep_grid = grx_grid(n, KC_BLOCK, KC_MAX_BLOCKS);
+    const unsigned init_grid = grx_grid(n, KC_BLOCK, KC_MAX_BLOCKS);
     const unsigned peel_grid = grx_grid(n, KC_BLOCK / KC_GROUP, KC_MAX_BLOCKS);
 
-    kc_init_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, d_row_ptr, d_in_row_ptr, s);
+    kc_init_kernel<<<init_grid, KC_BLOCK, 0, st>>>(n, d_row_ptr, d_in_row_ptr, s);
     if (n_hub_rows)
         kc_hub_flag_kernel<<<(unsigned)grx_ceil_div(n_hub_rows, KC_BLOCK), KC_BLOCK, 0, st>>>(
             n, d_hub_rows, n_hub_rows, directed ? KC_OUT_HUB : KC_OUT_HUB | KC_IN_HUB, s.state);
@@ -334,9 +231,8 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
     int32_t h[2];
     // every round but the last removes a node: at most n rounds
     const int rc = grx_run_rounds(
-        "grx_core_numbers: the peeling did not end after %lld rounds", KC_ROUND_BATCH, n + 1, 2, s.ctrl, h, st, [&] {
-            kc_min_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, s);
-            kc_collect_kernel<<<sweep_grid, KC_BLOCK, 0, st>>>(n, s);
+        "grx_core_numbers: the peeling did not end after %lld rounds", KC_ROUND_BATCH, n + 1, 2, s.pl.ctrl, h, st, [&] {
+            pl_sweeps(n, s, st);
             if (n_hub_rows)
                 kc_hub_kernel<<<(unsigned)n_hub_rows, KC_BLOCK, 0, st>>>(n, d_row_ptr, d_col, d_hub_rows, KC_IN_HUB,
                                                                          s);
@@ -345,11 +241,11 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
                                                                             KC_OUT_HUB, s);
             kc_peel_kernel<<<peel_grid, KC_BLOCK, 0, st>>>(d_row_ptr, d_col, hub_degree, d_in_row_ptr, d_in_col,
                                                            in_hub_degree, s);
-            kc_finalize_kernel<<<1, 1, 0, st>>>(s);
+            pl_finalize_kernel<<<1, 1, 0, st>>>(s.pl.ctrl);
             return (int)GRX_OK;
         });
     if (rc != GRX_OK) return rc;
-    if (n_rounds) *n_rounds = h[KT_LAYER];
+    if (n_rounds) *n_rounds = h[PL_ROUND];
     return GRX_OK;
 }
 

@@ -3,7 +3,8 @@
 // network analysis", 2008) -- the maximal subgraph in which every edge lies in at least k - 2 triangles of that
 // subgraph.  networkx peels one k per call, edge by edge in Python; here every k comes from one level-synchronous
 // peeling of the EDGES, the scheme of PKT (Kabir and Madduri, "Shared-memory graph truss decomposition", HiPC 2017),
-// which is grx_kcore.hip with edges for nodes and a row intersection for a row walk:
+// which is the peeling of grx_peel.h -- the one grx_kcore.hip runs over nodes -- with edges for items and a row
+// intersection for a row walk:
 //
 //   sup(e) = |N(u) & N(v)| for every edge e = (u, v)                          the triangles through e
 //   k = 2, round = 1, every edge alive
@@ -28,18 +29,15 @@
 // triangle exactly the one with the smallest id sends the decrement.
 //
 // Support pass: rj_arc_kernel of grx_rowjoin.h with a counting body, the intersection for the arcs with row < column
-// only (the other arc of the edge would count the same triangles).  The frontier is a list: of all the decrements an
-// edge receives exactly one takes it from above k - 2 to k - 2 (integer atomicSub returns the value before); that
-// thread writes t(e) at both arcs and the state word, and appends e to the next list through the LDS buffer of its
-// workgroup (one global atomic per workgroup and round on the list counter).  Only when the next list comes out empty
-// (k must jump) do two sweeps over the arcs run: tr_min (a wavefront reduction, one integer atomicMin per workgroup)
-// and tr_collect (F by the new k, one atomic per wavefront).  A lane group per frontier edge walks the shorter row and
+// only (the other arc of the edge would count the same triangles).  The frontier is grx_peel.h's list: of all the
+// decrements an edge receives exactly one takes it from above k - 2 to k - 2; that thread writes t(e) at both arcs and
+// the state word, and appends e to the next list.  The sweeps of a round whose list came out empty (k must jump) run
+// over the arcs, and the levels word counts them.  A lane group per frontier edge walks the shorter row and
 // binary-searches the longer one, as rj_arc_kernel does; it is the list-driven variant of that loop, written here
 // because its unit of work is a list entry and its hits need no reduction; a frontier edge whose support has reached 0
-// (every edge of truss number 2, for one) has no triangle left and is not intersected.  A one-thread finalize closes
-// the round; the rounds run as a device-steered round loop (grx_common.h).  Node column: rj_rows_kernel /
-// rj_hub_rows_kernel with a max body.  Measured: profiles/truss.txt (the peel waits for the longest hub-hub
-// intersection of every round).
+// (every edge of truss number 2, for one) has no triangle left and is not intersected.  Node column: rj_rows_kernel /
+// rj_hub_rows_kernel with a max body.  Measured: profiles/truss.txt (tr_min / tr_collect / tr_finalize there are
+// today's pl_* kernels; the peel waits for the longest hub-hub intersection of every round).
 // Bound: one row intersection per edge for the supports and one more per edge over the whole peel (each min(d_u, d_v) *
 // ceil(log2 max(d_u, d_v)) dependent 4-byte gathers), two 4-byte state gathers per common neighbour, at most three
 // atomic decrements per triangle (two when its first edge leaves alone, one when two leave together), one append per
@@ -51,19 +49,14 @@
 // exact small integers its reductions carry.
 #pragma clang fp contract(off)
 
+#include "grx_peel.h"
 #include "grx_rowjoin.h"
-
-#include <climits>
 
 namespace {
 
 constexpr int TR_ROUND_BATCH = 16;                           // rounds enqueued between two read-backs
-constexpr int TR_SWEEP_MAX_WG = 2048;
 constexpr int TR_PEEL_MAX_WG = 2048;
-constexpr int TR_APPEND_CAP = 2048;                          // LDS append buffer of a workgroup (entries)
-
-enum { TT_DONE = 0, TT_ROUND, TT_THR, TT_MIN, TT_SWEEP, TT_ALIVE, TT_CNT0, TT_CNT1, TT_LEVELS, TT_WORDS };
-static_assert(TT_WORDS <= GRX_CTRL_MAX_WORDS, "control words: one pinned block");
+static_assert(RJ_BLOCK == PL_BLOCK, "tr_peel_kernel flushes with pl_flush");
 
 // the workspace: arc_row | rev | sup | state | list0 | list1 (int32[nnz] each) | control words.  A list holds nnz / 2
 // edges at most; it has room for every position with row < column of a CSR that breaks the symmetry it promised
@@ -76,14 +69,25 @@ struct TrWs {
     size_t bytes() const { return 6 * arc + 256; }
 };
 
+// and the items of grx_peel.h: an edge (the position of its arc with row < column), alive while its state word is 0,
+// valued by sup against thr = k - 2
 struct TrState {
-    int32_t *arc_row, *rev, *sup, *state, *list0, *list1, *ctrl;
+    int32_t *arc_row, *rev, *sup, *state;
+    PlLists pl;
     int32_t *truss;                                          // the caller's [nnz]
+    __device__ __forceinline__ bool alive(int64_t j) const { return state[j] == 0; }
+    __device__ __forceinline__ int value(int64_t j) const { return sup[j]; }
+    __device__ __forceinline__ void leave(int64_t a, int round, int thr) const
+    {
+        state[a] = round;
+        truss[a] = thr + 2;
+        truss[rev[a]] = thr + 2;
+    }
 };
 
 TrState carve(const TrWs &w, int32_t *truss)
 {
-    return TrState{w.at(0), w.at(1), w.at(2), w.at(3), w.at(4), w.at(5), w.at(6), truss};
+    return TrState{w.at(0), w.at(1), w.at(2), w.at(3), PlLists{w.at(4), w.at(5), w.at(6)}, truss};
 }
 
 // ---- support pass: the bodies of grx_rowjoin.h ------------------------------------------------------------------
@@ -132,81 +136,13 @@ struct tr_node {                                             // the node column:
 };
 
 // ---- peeling ----------------------------------------------------------------------------------------------------
-// what a round's kernels read from ctrl: the list of this round (F) and the one they append to
-struct TrRound {
-    int round, thr, count;                                   // thr = k - 2
-    const int32_t *cur;
-    int32_t *next, *next_count;
-};
-
-__device__ __forceinline__ TrRound round_of(const TrState &s)
-{
-    TrRound r;
-    r.round = s.ctrl[TT_ROUND];
-    r.thr = s.ctrl[TT_SWEEP] ? max(s.ctrl[TT_THR], s.ctrl[TT_MIN]) : s.ctrl[TT_THR];
-    const int odd = r.round & 1;
-    r.count = s.ctrl[TT_CNT0 + odd];
-    r.cur = odd ? s.list1 : s.list0;
-    r.next = odd ? s.list0 : s.list1;
-    r.next_count = &s.ctrl[TT_CNT0 + (odd ^ 1)];
-    return r;
-}
-
 // sup(a) -= 1; the one decrement that takes a from above k - 2 to k - 2 puts a into the next round's F
-__device__ __forceinline__ void drop(int32_t a, const TrRound &r, const TrState &s, int32_t *buf, int *bcount)
+__device__ __forceinline__ void drop(int32_t a, const PlRound &r, const TrState &s, PlAppends &ap)
 {
     const int old = atomicSub(&s.sup[a], 1);
-    if (old == r.thr + 1) {
-        s.state[a] = r.round + 1;
-        s.truss[a] = r.thr + 2;
-        s.truss[s.rev[a]] = r.thr + 2;
-        const int slot = atomicAdd(bcount, 1);
-        if (slot < TR_APPEND_CAP) buf[slot] = a;
-        else r.next[atomicAdd(r.next_count, 1)] = a;
-    }
-}
-
-// sweep 1 (only when the list is empty): min sup over the alive edges
-__global__ __launch_bounds__(RJ_BLOCK) void tr_min_kernel(int64_t nnz, TrState s)
-{
-    __shared__ int smin;
-    if (s.ctrl[TT_DONE] || !s.ctrl[TT_SWEEP]) return;
-    if (threadIdx.x == 0) smin = INT_MAX;
-    __syncthreads();
-    int m = INT_MAX;
-    for (int64_t j = (int64_t)blockIdx.x * RJ_BLOCK + threadIdx.x; j < nnz; j += (int64_t)gridDim.x * RJ_BLOCK)
-        if (s.state[j] == 0) m = min(m, s.sup[j]);
-#pragma unroll
-    for (int off = GRX_WAVE / 2; off > 0; off >>= 1) m = min(m, __shfl_xor(m, off, GRX_WAVE));
-    if (threadIdx.x % GRX_WAVE == 0 && m < INT_MAX) atomicMin(&smin, m);
-    __syncthreads();
-    if (threadIdx.x == 0 && smin < INT_MAX) atomicMin(&s.ctrl[TT_MIN], smin);
-}
-
-// sweep 2: F = the alive edges with sup <= max(thr, min), appended one atomic per wavefront
-__global__ __launch_bounds__(RJ_BLOCK) void tr_collect_kernel(int64_t nnz, TrState s)
-{
-    if (s.ctrl[TT_DONE] || !s.ctrl[TT_SWEEP]) return;
-    const int round = s.ctrl[TT_ROUND];
-    const int thr = max(s.ctrl[TT_THR], s.ctrl[TT_MIN]);
-    int32_t *cur = (round & 1) ? s.list1 : s.list0;
-    int32_t *cur_count = &s.ctrl[TT_CNT0 + (round & 1)];
-    const int lane = threadIdx.x % GRX_WAVE;
-    // the trip count is the same in every lane of the workgroup: the ballot sees every lane
-    for (int64_t first = (int64_t)blockIdx.x * RJ_BLOCK; first < nnz; first += (int64_t)gridDim.x * RJ_BLOCK) {
-        const int64_t j = first + threadIdx.x;
-        const bool leaves = j < nnz && s.state[j] == 0 && s.sup[j] <= thr;
-        const unsigned long long m = __ballot(leaves);
-        if (!m) continue;
-        int base = 0;
-        if (lane == 0) base = atomicAdd(cur_count, __popcll(m));
-        base = __shfl(base, 0, GRX_WAVE);
-        if (leaves) {
-            cur[base + __popcll(m & ((1ull << lane) - 1))] = (int32_t)j;
-            s.state[j] = round;
-            s.truss[j] = thr + 2;
-            s.truss[s.rev[j]] = thr + 2;
-        }
+    if (pl_crosses(old, 1, r.thr)) {
+        s.leave(a, r.round + 1, r.thr);
+        pl_append(a, r, ap);
     }
 }
 
@@ -215,11 +151,10 @@ template <int L>
 __global__ __launch_bounds__(RJ_BLOCK) void tr_peel_kernel(const int64_t *__restrict__ row_ptr,
                                                            const int32_t *__restrict__ col, TrState s)
 {
-    __shared__ int32_t buf[TR_APPEND_CAP];
-    __shared__ int bcount, base;
-    if (s.ctrl[TT_DONE]) return;
-    const TrRound r = round_of(s);
-    if (threadIdx.x == 0) bcount = 0;
+    __shared__ PlAppends ap;
+    if (s.pl.ctrl[PL_DONE]) return;
+    const PlRound r = round_of(s.pl);
+    if (threadIdx.x == 0) ap.count = 0;
     __syncthreads();
     constexpr int EPG = RJ_BLOCK / L;                       // edges per workgroup pass
     const int lane = threadIdx.x % L;
@@ -247,49 +182,19 @@ __global__ __launch_bounds__(RJ_BLOCK) void tr_peel_kernel(const int64_t *__rest
             if ((ta > 0 && ta < r.round) || (tb > 0 && tb < r.round)) continue;   // the triangle died earlier
             const bool fa = ta == r.round, fb = tb == r.round;
             if (!fa && !fb) {
-                drop(a, r, s, buf, &bcount);
-                drop(b, r, s, buf, &bcount);
+                drop(a, r, s, ap);
+                drop(b, r, s, ap);
             } else if (fa && !fb) {
-                if (e < a) drop(b, r, s, buf, &bcount);
+                if (e < a) drop(b, r, s, ap);
             } else if (fb && !fa) {
-                if (e < b) drop(a, r, s, buf, &bcount);
+                if (e < b) drop(a, r, s, ap);
             }
         }
     }
-    // the workgroup's buffered appends, one atomic on the list counter
-    __syncthreads();
-    const int c = min(bcount, TR_APPEND_CAP);
-    if (threadIdx.x == 0 && c) base = atomicAdd(r.next_count, c);
-    __syncthreads();
-    for (int i = threadIdx.x; i < c; i += RJ_BLOCK) r.next[base + i] = buf[i];
+    pl_flush(r, ap);
 }
 
-__global__ void tr_init_kernel(int64_t m, TrState s)
-{
-    s.ctrl[TT_DONE] = 0; s.ctrl[TT_ROUND] = 1; s.ctrl[TT_THR] = 0; s.ctrl[TT_MIN] = INT_MAX; s.ctrl[TT_SWEEP] = 1;
-    s.ctrl[TT_ALIVE] = (int32_t)m; s.ctrl[TT_CNT0] = 0; s.ctrl[TT_CNT1] = 0; s.ctrl[TT_LEVELS] = 0;
-}
-
-// one thread: F has left; the next round, or done when no edge is alive.  An empty next list asks for the sweeps
-__global__ void tr_finalize_kernel(TrState s)
-{
-    int32_t *ctrl = s.ctrl;
-    if (ctrl[TT_DONE]) return;
-    const int odd = ctrl[TT_ROUND] & 1;
-    if (ctrl[TT_SWEEP]) {
-        ctrl[TT_THR] = max(ctrl[TT_THR], ctrl[TT_MIN]);
-        ctrl[TT_LEVELS] += 1;                                // every sweep finds a k above the last one
-    }
-    ctrl[TT_ALIVE] -= ctrl[TT_CNT0 + odd];
-    ctrl[TT_CNT0 + odd] = 0;
-    ctrl[TT_MIN] = INT_MAX;
-    if (ctrl[TT_ALIVE] <= 0) {
-        ctrl[TT_DONE] = 1;                                  // TT_ROUND stays: the number of rounds run
-        return;
-    }
-    ctrl[TT_SWEEP] = ctrl[TT_CNT0 + (odd ^ 1)] == 0;
-    ctrl[TT_ROUND] += 1;
-}
+__global__ void tr_init_kernel(int64_t m, TrState s) { pl_init_ctrl(s.pl.ctrl, (int32_t)m); }
 
 }  // namespace
 
@@ -341,24 +246,22 @@ int grx_truss_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
                     tr_rows{nullptr}, false);
     if (rc != GRX_OK) return rc;
 
-    const unsigned sweep_grid = grx_grid(c.nnz, RJ_BLOCK, TR_SWEEP_MAX_WG);
-    int32_t h[TT_WORDS];
+    int32_t h[PL_WORDS];
     rj_with_lanes(lanes_per_row, [&](auto width) {
         constexpr int L = decltype(width)::value;
         const unsigned peel_grid = grx_grid(m, RJ_BLOCK / L, TR_PEEL_MAX_WG);
         // every round removes at least one edge: at most m rounds
         rc = grx_run_rounds("grx_truss_numbers: the peeling did not end after %lld rounds", TR_ROUND_BATCH, m + 1,
-                            TT_WORDS, s.ctrl, h, c.st, [&] {
-                                tr_min_kernel<<<sweep_grid, RJ_BLOCK, 0, c.st>>>(c.nnz, s);
-                                tr_collect_kernel<<<sweep_grid, RJ_BLOCK, 0, c.st>>>(c.nnz, s);
+                            PL_WORDS, s.pl.ctrl, h, c.st, [&] {
+                                pl_sweeps(c.nnz, s, c.st);
                                 tr_peel_kernel<L><<<peel_grid, RJ_BLOCK, 0, c.st>>>(d_row_ptr, d_col, s);
-                                tr_finalize_kernel<<<1, 1, 0, c.st>>>(s);
+                                pl_finalize_kernel<<<1, 1, 0, c.st>>>(s.pl.ctrl);
                                 return (int)GRX_OK;
                             });
     });
     if (rc != GRX_OK) return rc;
-    if (n_rounds) *n_rounds = h[TT_ROUND];
-    if (n_levels) *n_levels = h[TT_LEVELS];
+    if (n_rounds) *n_rounds = h[PL_ROUND];
+    if (n_levels) *n_levels = h[PL_LEVELS];
 
     if (d_node_truss) {
         const tr_node node{d_arc_truss, d_node_truss};

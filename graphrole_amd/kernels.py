@@ -25,8 +25,9 @@ SQ_LDS_MAX_WEDGES = 3072     # LDS table, up to this many in a four-wavefront on
 # The caps of the other grid-stride launches, grx_grid(items, per_block, cap): a launch takes a second trip of its loop
 # when items > cap * per_block.  tests/test_gpu_second_trip.py sizes its graphs by these copies and
 # tests/test_tiled_graphs_cpu.py reads every value back from the source named here.
-TR_SWEEP_MAX_WG = 2048       # csrc/grx_truss.hip: workgroups of the per-arc sweeps (256 arcs each)
-TR_PEEL_MAX_WG = 2048        # and of the peel (256 / lanes frontier edges each)
+PL_BLOCK = 256               # csrc/grx_peel.h (grx_core_numbers, grx_truss_numbers): threads per workgroup
+PL_SWEEP_MAX_WG = 2048       # and workgroups of the two sweeps over all items (256 nodes resp. arcs each)
+TR_PEEL_MAX_WG = 2048        # csrc/grx_truss.hip: workgroups of the peel (256 / lanes frontier edges each)
 GL_K4_MAX_WG = 8192          # csrc/grx_graphlets.hip: workgroups of the 4-clique kernel (256 / lanes arcs each)
 SQ_WAVE_MAX_WG = 8192        # csrc/grx_square_clustering.hip: workgroups of the wave tier (64 rows each),
 SQ_LDS_MAX_WG = 1024         # of the LDS tier (256 rows each)

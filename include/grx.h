@@ -1064,7 +1064,8 @@ int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
  *   which networkx does not define.  PRECONDITION: no self-loop entry in either CSR (networkx raises
  *   NetworkXNotImplemented for such a graph; the caller refuses it).  Weights are not read.  Rows longer than
  *   GRX_HUB_FACTOR * lanes_per_row (in_lanes_per_row) must be listed in d_hub_rows (d_in_hub_rows).
- *   Method: see the header of csrc/grx_kcore.hip.  The next round's nodes are collected in a list by the decrement
+ *   Method: see the headers of csrc/grx_kcore.hip and csrc/grx_peel.h (the peeling core it shares with
+ *   grx_truss_numbers).  The next round's nodes are collected in a list by the decrement
  *   that takes a node's degree from above k to k or below; all n nodes are swept (twice) only when k jumps.  Cost: 2
  *   sweeps per distinct core value, every arc visited once from each end over the whole run, and every alive hub row
  *   read once per round (a hub pulls its decrement instead of taking one atomic per leaving neighbour).  16 rounds
@@ -1207,7 +1208,8 @@ int grx_square_clustering(int64_t n, const int64_t *d_row_ptr, const int32_t *d_
  *   d_arc_truss: int32[nnz], overwritten: t of the edge at BOTH of its arcs.
  *   d_node_truss: int64[n] or NULL.
  *   n_rounds: HOST int64 or NULL: the number of rounds run.  n_levels: HOST int64 or NULL: the distinct k assigned.
- *   Method: see the header of csrc/grx_truss.hip.  The supports are one row intersection per edge (the per-arc kernel
+ *   Method: see the headers of csrc/grx_truss.hip and csrc/grx_peel.h (the peeling core it shares with
+ *   grx_core_numbers).  The supports are one row intersection per edge (the per-arc kernel
  *   of csrc/grx_rowjoin.h at the arcs with row < column; the position of every arc's reverse by one binary search
  *   beside it); the next round's edges are collected in a list by the decrement that takes an edge's support from
  *   above k - 2 to k - 2; all arcs are swept (twice) only when k jumps.  Cost: 2 intersections per edge over the whole

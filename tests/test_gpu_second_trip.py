@@ -16,8 +16,9 @@ graph, and
   tolerance, with the motif's oracle answer tiled (tests/test_tiled_graphs_cpu.py proves that construction);
 * asserts the bytes of the kernel's own one-trip run on the motif alone, tiled, with the same lanes / batch / words.
 
-Not wrapped here: ec_level with words = 1 needs more than 8192 * 256 = 2 M rows, above the size limit of this file
-(2^21 rows); words = 16 wraps the same kernels above 131 072 rows.  The other second-trip tests of the suite:
+Not wrapped here: ms_level (the level kernel of grx_closeness.hip, run here with grx_eccentricity's bodies) with
+words = 1 needs more than 8192 * 256 = 2 M rows, above the size limit of this file (2^21 rows); words = 16 wraps the
+same kernels above 131 072 rows.  The other second-trip tests of the suite:
 measures_oracle.GRAPHS['rows32' | 'rows4' | 'elements'], test_second_trip_of_the_grid_stride_loops in
 test_gpu_clustering.py and test_gpu_structural_holes.py, aggx_oracle.LENGTHS, and the full-size tests (ReFeX, closeness,
 betweenness, k-core, role rows).
@@ -77,7 +78,7 @@ def test_truss_numbers():
     want = to.truss_numbers(m.row_ptr, m.col)
     assert want.n_levels > 1 and want.n_rounds > 3
     for lanes in (32, big.lanes_per_row):
-        assert _wraps(nnz, K.RJ_BLOCK, K.TR_SWEEP_MAX_WG)                       # tr_min, tr_collect
+        assert _wraps(nnz, K.PL_BLOCK, K.PL_SWEEP_MAX_WG)                       # pl_min, pl_collect over the arcs
         assert _wraps(nnz // 2, K.RJ_BLOCK // lanes, K.TR_PEEL_MAX_WG)          # tr_peel<L>
         assert _wraps(n, K.RJ_BLOCK // lanes, K.RJ_ROW_MAX_WG)                  # rj_rows<L>: support and node truss
         assert _wraps(nnz, K.RJ_BLOCK // lanes, K.RJ_ARC_MAX_WG)                # rj_arc<L>
@@ -268,13 +269,13 @@ def test_weighted_betweenness(kind):
 
 # ----------------------------------------------------------------------------------------------------- eccentricity
 def test_eccentricity_pass():
-    """words = 16: ec_level<16, BOUNDS> takes 256 / 16 rows a workgroup and wraps above 131 072 rows -- without the
+    """words = 16: ms_level<16, Body> takes 256 / 16 rows a workgroup and wraps above 131 072 rows -- without the
     bounds (no upper), with them (want_upper), and continuing from carried bounds.  words = 1 would need more than
     2 M rows and stays out."""
     from graphrole_amd import kernels as K
     (m, C, n, row_ptr, col, _, _), big, small = _pair(K, 'structural')
     words = 16
-    assert _wraps(n, K.CL_BLOCK // words, K.CL_MAX_ROW_BLOCKS)                  # ec_level<W, false>, ec_level<W, true>
+    assert _wraps(n, K.CL_BLOCK // words, K.CL_MAX_ROW_BLOCKS)                  # ms_level<W, ec_reach>, <W, ec_bounds>
     first, second = tg.spread_sources(m.n, C, 70, seed=1), tg.spread_sources(m.n, C, 30, seed=2)
     assert first.max() > ROWS and second.max() > ROWS
 

@@ -67,8 +67,8 @@ def child(case):
 
 
 def kernel_split(case):
-    """{kernel: launches and ms per call} of the kc_* kernels from a rocprofv3 run of `--child case` (two calls:
-    halved)."""
+    """{kernel: launches and ms per call} of the kc_* kernels and the pl_* ones of grx_peel.h from a rocprofv3 run of
+    `--child case` (two calls: halved)."""
     if shutil.which('rocprofv3') is None:
         return {'error': 'rocprofv3 not found'}
     out_dir = tempfile.mkdtemp(prefix='kc_prof_')
@@ -82,9 +82,10 @@ def kernel_split(case):
         for path in glob.glob(os.path.join(out_dir, '**', '*kernel_stats.csv'), recursive=True):
             for row in csv.DictReader(open(path)):
                 name = row.get('Name', '')
-                if 'kc_' not in name:
+                prefix = next((p for p in ('kc_', 'pl_') if p in name), None)
+                if prefix is None:
                     continue
-                key = name[name.index('kc_'):].split('(')[0]
+                key = name[name.index(prefix):].split('(')[0].split('<')[0]
                 split[key] = {'calls': int(row['Calls']) // 2,
                               'ms': round(float(row['TotalDurationNs']) / 2e6, 4)}
         return dict(sorted(split.items(), key=lambda kv: -kv[1]['ms'])) or {'error': 'no kernel_stats.csv rows'}

@@ -38,7 +38,7 @@ sys.path.insert(0, ROOT)
 GRAPHS = ('ba_m10', 'ba_m2', 'bipartite')
 #: kernel-name fragment -> stage of the split
 STAGES = (('tr_support', 'support'), ('tr_rows', 'support_rows'), ('tr_node', 'node'), ('tr_peel', 'peel'),
-          ('tr_min', 'sweep_min'), ('tr_collect', 'sweep_collect'), ('tr_finalize', 'finalize'), ('tr_init', 'init'))
+          ('pl_min', 'sweep_min'), ('pl_collect', 'sweep_collect'), ('pl_finalize', 'finalize'), ('tr_init', 'init'))
 
 
 def _csr(name, n):
