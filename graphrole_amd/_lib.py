@@ -266,6 +266,15 @@ _SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
                                          c_double, c_int, c_void_p, POINTER(c_int64), POINTER(c_int64), c_void_p,
                                          c_size_t, c_void_p]),
+    'grx_edge_betweenness_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
+    'grx_edge_betweenness': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_int, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
+    'grx_weighted_edge_betweenness_workspace_bytes': (c_size_t, [c_int64, c_int, c_int64]),
+    'grx_weighted_edge_betweenness': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                              c_int64, c_double, c_int, c_void_p, POINTER(c_int64), POINTER(c_int64),
+                                              c_void_p, c_size_t, c_void_p]),
     'grx_biconnected_workspace_bytes': (c_size_t, [c_int64]),
     'grx_biconnected': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int64), c_void_p, c_size_t, c_void_p]),

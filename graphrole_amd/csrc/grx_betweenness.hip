@@ -18,11 +18,22 @@
 //   batch in lane order, batches in order), so the result has the same bits for every B.  A final kernel
 //   multiplies by the scale of _rescale.  No floating-point atomics (the per-lane reach counts are integer adds).
 //
+// grx_edge_betweenness (networkx's edge_betweenness_centrality, _accumulate_edges, _rescale_e) runs the same forward and
+// backward kernels with coeff written to an array of its own (the backward kernels are templated on that), so that
+// sigma survives; after the backward loop of a batch one pass over the arcs adds sigma(v) * coeff(w) -- the term the
+// backward pass formed -- of every DAG arc v -> w onto the arc's slot.  One wavefront per row (hub rows: a workgroup,
+// its four wavefronts take every fourth arc), the lanes are the batch's sources, so a slot is written by one wavefront
+// and every read of level, sigma and coeff is one contiguous load.  The order of the additions is that of
+// grx_edge_sum.h: a fixed tree over each aligned group of 16 consecutive sources, the groups one after another in
+// source order -- the same bits for every B.  The unused lanes of a partial batch (BW_IDLE) hold +0.0.  Undirected: the
+// edge is the sum of its two arc slots, taken by grx_edge_sum.h's final passes together with the scale of _rescale_e.
+//
 // Compiled with -ffp-contract=off (Makefile; the pragma carries it with the file): every product and sum is its own
 // IEEE operation, as in networkx.
 #pragma clang fp contract(off)
 
 #include "grx_common.h"
+#include "grx_edge_sum.h"
 
 #include <algorithm>
 
@@ -40,29 +51,33 @@ constexpr int32_t BW_IDLE = 0x7fffffff;
 
 // B of batch = 0: the widest multiple of 64 up to 256 whose state fits BW_DEFAULT_STATE_BYTES (at least 64, so above
 // ~3.35 M nodes the state is 20 n 64 bytes, more than the budget), and no wider than the source list
-int choose_batch(int64_t n, int batch, int64_t n_sources)
+// (grx_edge_betweenness: 28 bytes per cell, coeff has an array of its own)
+int choose_batch(int64_t n, int batch, int64_t n_sources, bool keep_sigma = false)
 {
     if (batch > 0) return batch;
-    const size_t per_lane = (size_t)(n > 0 ? n : 1) * 20;   // level 4 + sigma 8 + delta 8 bytes per (node, source)
+    // level 4 + sigma 8 + delta 8 (+ coeff 8) bytes per (node, source)
+    const size_t per_lane = (size_t)(n > 0 ? n : 1) * (keep_sigma ? 28 : 20);
     const int64_t b = (int64_t)(BW_DEFAULT_STATE_BYTES / per_lane) / GRX_WAVE * GRX_WAVE;
     const int64_t widest = std::max<int64_t>(GRX_WAVE, std::min<int64_t>(b, BW_MAX_BATCH));
     const int64_t needed = std::max<int64_t>(GRX_WAVE, grx_ceil_div(n_sources, GRX_WAVE) * GRX_WAVE);
     return (int)std::min<int64_t>(widest, needed);
 }
 
-size_t ws_bytes(int64_t n, int B)
+size_t ws_bytes(int64_t n, int B, bool keep_sigma = false)
 {
     const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)B;
-    return grx_align_up(cells * 4, 256) + 2 * grx_align_up(cells * 8, 256) + grx_align_up((size_t)B * 4, 256) + 256;
+    return grx_align_up(cells * 4, 256) + (keep_sigma ? 3 : 2) * grx_align_up(cells * 8, 256) +
+           grx_align_up((size_t)B * 4, 256) + 256;
 }
 
 struct BwWs {
     int32_t *level;
     double *sigma, *delta;
+    double *coeff;                                           // grx_edge_betweenness only; otherwise coeff replaces sigma
     int32_t *reach, *ctrl;
 };
 
-BwWs carve(void *base, int64_t n, int B)
+BwWs carve(void *base, int64_t n, int B, bool keep_sigma = false)
 {
     const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)B;
     char *p = reinterpret_cast<char *>(base);
@@ -70,6 +85,8 @@ BwWs carve(void *base, int64_t n, int B)
     w.level = reinterpret_cast<int32_t *>(p); p += grx_align_up(cells * 4, 256);
     w.sigma = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
     w.delta = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
+    w.coeff = nullptr;
+    if (keep_sigma) { w.coeff = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256); }
     w.reach = reinterpret_cast<int32_t *>(p); p += grx_align_up((size_t)B * 4, 256);
     w.ctrl = reinterpret_cast<int32_t *>(p);
     return w;
@@ -223,20 +240,24 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_forward_hub_kernel(const int64_t 
 }
 
 // networkx _accumulate_*: coeff = (1 + delta[w]) / sigma[w]; delta[v] += sigma[v] * coeff
-__device__ __forceinline__ void settle(int64_t cell, double d, double sv, double *__restrict__ sigma,
+__device__ __forceinline__ void settle(int64_t cell, double d, double sv, double *__restrict__ coeff,
                                        double *__restrict__ delta)
 {
     delta[cell] = d;
-    sigma[cell] = (1.0 + d) / sv;                            // coeff(v) for the level above
+    coeff[cell] = (1.0 + d) / sv;                            // coeff(v) for the level above
 }
 
-// backward, level l: cells at level l pull delta from their successors at l + 1; one wavefront per (row, chunk)
+// backward, level l: cells at level l pull delta from their successors at l + 1; one wavefront per (row, chunk).
+// KEEP_SIGMA = false: coeff replaces sigma in place (kept_coeff is not read); true: coeff goes to kept_coeff
+template <bool KEEP_SIGMA>
 __global__ __launch_bounds__(BW_BLOCK) void bw_backward_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
                                                                const int32_t *__restrict__ col, int64_t hub_degree,
                                                                int B, int l, const int32_t *__restrict__ level,
                                                                double *__restrict__ sigma,
+                                                               double *__restrict__ kept_coeff,
                                                                double *__restrict__ delta)
 {
+    double *coeff = KEEP_SIGMA ? kept_coeff : sigma;
     const int lane = threadIdx.x % GRX_WAVE;
     const int off = blockIdx.y * GRX_WAVE + lane;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / GRX_WAVE);
@@ -247,19 +268,22 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_backward_kernel(int64_t n, const 
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
         if (e - b > hub_degree) continue;                   // bw_backward_hub_kernel
         const double sv = mine ? sigma[cell] : 1.0;
-        const double d = pull_delta(b, e, 1, col, level, sigma, B, off, l + 1, sv);
-        if (mine) settle(cell, d, sv, sigma, delta);
+        const double d = pull_delta(b, e, 1, col, level, coeff, B, off, l + 1, sv);
+        if (mine) settle(cell, d, sv, coeff, delta);
     }
 }
 
+template <bool KEEP_SIGMA>
 __global__ __launch_bounds__(BW_BLOCK) void bw_backward_hub_kernel(const int64_t *__restrict__ row_ptr,
                                                                    const int32_t *__restrict__ col,
                                                                    const int32_t *__restrict__ hub_rows, int B, int l,
                                                                    const int32_t *__restrict__ level,
                                                                    double *__restrict__ sigma,
+                                                                   double *__restrict__ kept_coeff,
                                                                    double *__restrict__ delta)
 {
     __shared__ double part[BW_WAVES][GRX_WAVE];
+    double *coeff = KEEP_SIGMA ? kept_coeff : sigma;
     const int lane = threadIdx.x % GRX_WAVE, wave = threadIdx.x / GRX_WAVE;
     const int off = blockIdx.y * GRX_WAVE + lane;
     const int64_t v = hub_rows[blockIdx.x];
@@ -268,10 +292,10 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_backward_hub_kernel(const int64_t
     if (!__ballot(mine)) return;
     const int64_t b = row_ptr[v], e = row_ptr[v + 1];
     const double sv = mine ? sigma[cell] : 1.0;
-    part[wave][lane] = pull_delta(b + wave, e, BW_WAVES, col, level, sigma, B, off, l + 1, sv);
+    part[wave][lane] = pull_delta(b + wave, e, BW_WAVES, col, level, coeff, B, off, l + 1, sv);
     __syncthreads();
     if (wave != 0 || !mine) return;
-    settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, sigma, delta);
+    settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, coeff, delta);
 }
 
 // bc[v] += the contributions of the batch's sources in lane order (networkx: betweenness[w] += delta[w] for w != s;
@@ -301,6 +325,150 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_scale_kernel(int64_t n, double sc
         bc[v] *= scale;
 }
 
+
+// grx_edge_betweenness, after the backward loop of a batch: the arcs [b, e) with stride `step` of row v, the wavefront's
+// lanes being the sources of one 64-lane chunk after another.  Lane `off` holds sigma(v) * coeff(w) when v -> w is an
+// arc of its source's BFS DAG (level(w) == level(v) + 1) and +0.0 otherwise; grx_edge_sum.h's order adds them onto the
+// slot.  A slot is read and written by lane 0 of the one wavefront that owns it.
+__device__ __forceinline__ void edge_row(int64_t v, int64_t b, int64_t e, int step, const int32_t *__restrict__ col,
+                                         const int32_t *__restrict__ level, const double *__restrict__ sigma,
+                                         const double *__restrict__ coeff, int B, int lane, double *__restrict__ ebc)
+{
+    for (int64_t j = b; j < e; j += step) {
+        const int64_t w = col[j];
+        double acc = 0.0;
+        bool any = false;
+        for (int off = lane; off < B; off += GRX_WAVE) {
+            const int lv = level[v * B + off];
+            const bool on = lv >= 0 && lv != BW_IDLE && level[w * B + off] == lv + 1;
+            if (!__ballot(on)) continue;                    // 64 times +0.0
+            if (!any && lane == 0) acc = ebc[j];
+            any = true;
+            acc = eb_add_groups<GRX_WAVE>(acc, on ? sigma[v * B + off] * coeff[w * B + off] : 0.0, 0);
+        }
+        if (any && lane == 0) ebc[j] = acc;
+    }
+}
+
+// rows up to hub_degree arcs: one wavefront per row
+__global__ __launch_bounds__(BW_BLOCK) void bw_edge_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+                                                           const int32_t *__restrict__ col, int64_t hub_degree, int B,
+                                                           const int32_t *__restrict__ level,
+                                                           const double *__restrict__ sigma,
+                                                           const double *__restrict__ coeff, double *__restrict__ ebc)
+{
+    const int lane = threadIdx.x % GRX_WAVE;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / GRX_WAVE);
+    for (int64_t v = (int64_t)blockIdx.x * BW_WAVES + wave; v < n; v += (int64_t)gridDim.x * BW_WAVES) {
+        const int64_t b = row_ptr[v], e = row_ptr[v + 1];
+        if (e - b > hub_degree) continue;                   // bw_edge_hub_kernel
+        edge_row(v, b, e, 1, col, level, sigma, coeff, B, lane, ebc);
+    }
+}
+
+// hub rows: one workgroup per hub row; the four wavefronts take every fourth arc (a slot still has one owner)
+__global__ __launch_bounds__(BW_BLOCK) void bw_edge_hub_kernel(const int64_t *__restrict__ row_ptr,
+                                                               const int32_t *__restrict__ col,
+                                                               const int32_t *__restrict__ hub_rows, int B,
+                                                               const int32_t *__restrict__ level,
+                                                               const double *__restrict__ sigma,
+                                                               const double *__restrict__ coeff,
+                                                               double *__restrict__ ebc)
+{
+    const int lane = threadIdx.x % GRX_WAVE;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / GRX_WAVE);
+    const int64_t v = hub_rows[blockIdx.x];
+    edge_row(v, row_ptr[v] + wave, row_ptr[v + 1], BW_WAVES, col, level, sigma, coeff, B, lane, ebc);
+}
+
+// Both entry points: EDGES = false is grx_betweenness (d_out = bc, one value per node), true is grx_edge_betweenness
+// (d_out = ebc, one value per arc of the out CSR; `endpoints` is not read)
+template <bool EDGES>
+int run(const char *name, int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+        int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+        const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, const int32_t *d_sources,
+        int64_t n_sources, int endpoints, double scale, int batch, double *d_out, void *d_workspace,
+        size_t workspace_bytes, void *stream)
+{
+    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "%s: n = %lld out of range", name, (long long)n);
+    GRX_REQUIRE(d_row_ptr && d_col && d_out && d_workspace, "%s: null pointer", name);
+    GRX_REQUIRE(n_sources >= 0 && (n_sources == 0 || d_sources), "%s: source list", name);
+    GRX_REQUIRE(batch == 0 || (batch > 0 && batch <= BW_MAX_BATCH && batch % GRX_WAVE == 0),
+                "%s: batch must be 0 or a multiple of 64 up to %d (got %d)", name, BW_MAX_BATCH, batch);
+    const bool directed = d_in_row_ptr != nullptr;
+    GRX_REQUIRE(!directed || d_in_col, "%s: d_in_col is required with d_in_row_ptr", name);
+    if (!directed) {                                         // undirected: the CSR is its own in-adjacency
+        d_in_col = d_col;
+        d_in_hub_rows = d_hub_rows;
+        n_in_hub_rows = n_hub_rows;
+        in_lanes_per_row = lanes_per_row;
+    }
+    GRX_REQUIRE(lanes_per_row >= 1 && in_lanes_per_row >= 1, "%s: lanes_per_row must be >= 1", name);
+    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows) && n_in_hub_rows >= 0 &&
+                    (n_in_hub_rows == 0 || d_in_hub_rows), "%s: hub list", name);
+    const int B = choose_batch(n, batch, n_sources, EDGES);
+    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, B, EDGES), "%s: workspace %zu bytes, need %zu", name, workspace_bytes,
+                ws_bytes(n, B, EDGES));
+    hipStream_t st = grx_stream(stream);
+    const BwWs ws = carve(d_workspace, n, B, EDGES);
+    const int chunks = B / GRX_WAVE;
+    const unsigned egrid = grx_grid(n, BW_BLOCK, BW_MAX_BLOCKS);
+    const unsigned row_blocks = grx_grid(n, BW_WAVES, BW_MAX_ROW_BLOCKS);
+    const dim3 row_grid(row_blocks, (unsigned)chunks);
+    const int64_t out_hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
+    const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
+    const int64_t cells = n * (int64_t)B;
+    const int64_t *in_rp = directed ? d_in_row_ptr : d_row_ptr;
+
+    if (EDGES) eb_rows<EB_ZERO>(n, d_row_ptr, d_col, 0.0, d_out, st);
+    else grx_fill64(reinterpret_cast<uint64_t *>(d_out), n, 0, st);
+    GRX_LAUNCH_CHECK();
+    for (int64_t first = 0; first < n_sources; first += B) {
+        const int count = (int)std::min<int64_t>(B, n_sources - first);
+        bw_level_init_kernel<<<grx_grid(cells, BW_BLOCK, BW_MAX_BLOCKS), BW_BLOCK, 0, st>>>(cells, B, count, ws.level);
+        bw_source_init_kernel<<<1, BW_MAX_BATCH, 0, st>>>(n, B, count, d_sources + first, ws.level, ws.sigma, ws.reach,
+                                                          ws.ctrl);
+        GRX_LAUNCH_CHECK();
+        int32_t h[2];
+        // a BFS has at most n levels; one more launch finds the empty frontier
+        const int rc = grx_run_rounds(
+            EDGES ? "grx_edge_betweenness: the forward pass did not end after %lld levels"
+                  : "grx_betweenness: the forward pass did not end after %lld levels",
+            BW_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
+                if (n_in_hub_rows)
+                    bw_forward_hub_kernel<<<dim3((unsigned)n_in_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
+                        in_rp, d_in_col, d_in_hub_rows, B, ws.level, ws.sigma, ws.reach, ws.ctrl);
+                bw_forward_kernel<<<row_grid, BW_BLOCK, 0, st>>>(n, in_rp, d_in_col, in_hub_degree, B, ws.level,
+                                                                 ws.sigma, ws.reach, ws.ctrl);
+                return grx_frontier_advance(ws.ctrl, st);
+            });
+        if (rc != GRX_OK) return rc;
+        for (int l = h[GRX_CT_LEVEL]; l >= 1; --l) {        // deepest level first; the sources need no delta
+            if (n_hub_rows)
+                bw_backward_hub_kernel<EDGES><<<dim3((unsigned)n_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
+                    d_row_ptr, d_col, d_hub_rows, B, l, ws.level, ws.sigma, ws.coeff, ws.delta);
+            bw_backward_kernel<EDGES><<<row_grid, BW_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, l,
+                                                                     ws.level, ws.sigma, ws.coeff, ws.delta);
+            GRX_LAUNCH_CHECK();
+        }
+        if (EDGES) {
+            if (n_hub_rows)
+                bw_edge_hub_kernel<<<(unsigned)n_hub_rows, BW_BLOCK, 0, st>>>(d_row_ptr, d_col, d_hub_rows, B, ws.level,
+                                                                              ws.sigma, ws.coeff, d_out);
+            bw_edge_kernel<<<row_blocks, BW_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, ws.level, ws.sigma,
+                                                            ws.coeff, d_out);
+        } else {
+            bw_accumulate_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, B, count, endpoints, ws.level, ws.delta, ws.reach,
+                                                             d_out);
+        }
+        GRX_LAUNCH_CHECK();
+    }
+    if (EDGES) eb_finish(n, d_row_ptr, d_col, directed, scale, d_out, st);
+    else bw_scale_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, scale, d_out);
+    GRX_LAUNCH_CHECK();
+    return GRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -316,70 +484,25 @@ int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
                     const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch, double *d_bc,
                     void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_betweenness: n = %lld out of range", (long long)n);
-    GRX_REQUIRE(d_row_ptr && d_col && d_bc && d_workspace, "grx_betweenness: null pointer");
-    GRX_REQUIRE(n_sources >= 0 && (n_sources == 0 || d_sources), "grx_betweenness: source list");
-    GRX_REQUIRE(batch == 0 || (batch > 0 && batch <= BW_MAX_BATCH && batch % GRX_WAVE == 0),
-                "grx_betweenness: batch must be 0 or a multiple of 64 up to %d (got %d)", BW_MAX_BATCH, batch);
-    const bool directed = d_in_row_ptr != nullptr;
-    GRX_REQUIRE(!directed || d_in_col, "grx_betweenness: d_in_col is required with d_in_row_ptr");
-    if (!directed) {                                         // undirected: the CSR is its own in-adjacency
-        d_in_col = d_col;
-        d_in_hub_rows = d_hub_rows;
-        n_in_hub_rows = n_hub_rows;
-        in_lanes_per_row = lanes_per_row;
-    }
-    GRX_REQUIRE(lanes_per_row >= 1 && in_lanes_per_row >= 1, "grx_betweenness: lanes_per_row must be >= 1");
-    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows) && n_in_hub_rows >= 0 &&
-                    (n_in_hub_rows == 0 || d_in_hub_rows), "grx_betweenness: hub list");
-    const int B = choose_batch(n, batch, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, B), "grx_betweenness: workspace %zu bytes, need %zu", workspace_bytes,
-                ws_bytes(n, B));
-    hipStream_t st = grx_stream(stream);
-    const BwWs ws = carve(d_workspace, n, B);
-    const int chunks = B / GRX_WAVE;
-    const unsigned egrid = grx_grid(n, BW_BLOCK, BW_MAX_BLOCKS);
-    const dim3 row_grid(grx_grid(n, BW_WAVES, BW_MAX_ROW_BLOCKS), (unsigned)chunks);
-    const int64_t out_hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
-    const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
-    const int64_t cells = n * (int64_t)B;
-    const int64_t *in_rp = directed ? d_in_row_ptr : d_row_ptr;
+    return run<false>("grx_betweenness", n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr,
+                      d_in_col, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, endpoints, scale,
+                      batch, d_bc, d_workspace, workspace_bytes, stream);
+}
 
-    grx_fill64(reinterpret_cast<uint64_t *>(d_bc), n, 0, st);
-    GRX_LAUNCH_CHECK();
-    for (int64_t first = 0; first < n_sources; first += B) {
-        const int count = (int)std::min<int64_t>(B, n_sources - first);
-        bw_level_init_kernel<<<grx_grid(cells, BW_BLOCK, BW_MAX_BLOCKS), BW_BLOCK, 0, st>>>(cells, B, count, ws.level);
-        bw_source_init_kernel<<<1, BW_MAX_BATCH, 0, st>>>(n, B, count, d_sources + first, ws.level, ws.sigma, ws.reach,
-                                                          ws.ctrl);
-        GRX_LAUNCH_CHECK();
-        int32_t h[2];
-        // a BFS has at most n levels; one more launch finds the empty frontier
-        const int rc = grx_run_rounds(
-            "grx_betweenness: the forward pass did not end after %lld levels", BW_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st,
-            [&] {
-                if (n_in_hub_rows)
-                    bw_forward_hub_kernel<<<dim3((unsigned)n_in_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
-                        in_rp, d_in_col, d_in_hub_rows, B, ws.level, ws.sigma, ws.reach, ws.ctrl);
-                bw_forward_kernel<<<row_grid, BW_BLOCK, 0, st>>>(n, in_rp, d_in_col, in_hub_degree, B, ws.level,
-                                                                 ws.sigma, ws.reach, ws.ctrl);
-                return grx_frontier_advance(ws.ctrl, st);
-            });
-        if (rc != GRX_OK) return rc;
-        for (int l = h[GRX_CT_LEVEL]; l >= 1; --l) {        // deepest level first; the sources need no delta
-            if (n_hub_rows)
-                bw_backward_hub_kernel<<<dim3((unsigned)n_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
-                    d_row_ptr, d_col, d_hub_rows, B, l, ws.level, ws.sigma, ws.delta);
-            bw_backward_kernel<<<row_grid, BW_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, l, ws.level,
-                                                              ws.sigma, ws.delta);
-            GRX_LAUNCH_CHECK();
-        }
-        bw_accumulate_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, B, count, endpoints, ws.level, ws.delta, ws.reach, d_bc);
-        GRX_LAUNCH_CHECK();
-    }
-    bw_scale_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, scale, d_bc);
-    GRX_LAUNCH_CHECK();
-    return GRX_OK;
+size_t grx_edge_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources)
+{
+    return ws_bytes(n, choose_batch(n, batch, n_sources, true), true);
+}
+
+int grx_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                         int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+                         const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
+                         const int32_t *d_sources, int64_t n_sources, double scale, int batch, double *d_ebc,
+                         void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return run<true>("grx_edge_betweenness", n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr,
+                     d_in_col, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, 0, scale, batch,
+                     d_ebc, d_workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -43,9 +43,20 @@
 // Hub rows (longer than GRX_HUB_FACTOR * lanes_per_row of the CSR the pass reads) get a workgroup each in both passes:
 //   WB_PARTS = 4 lane groups of S lanes take every fourth arc and combine as ((p0 + p1) + p2) + p3 -- four parts for
 //   every S, so that the order of the additions does not depend on the batch width.
+//
+// grx_weighted_edge_betweenness (networkx's edge_betweenness_centrality with a weight, _accumulate_edges, _rescale_e)
+// runs the same relaxation, forward and backward kernels with coeff written to an array of its own (the backward
+// kernels are templated on that: 36 bytes per cell), so that sigma survives; after the backward loop of a batch one pass
+// over the arcs adds sigma(v) * coeff(x) of every DAG arc v -> x (the tight-arc test above, v resolved, x deeper) onto
+// the arc's slot.  S lanes per row (hub rows: a workgroup whose WB_PARTS lane groups take every fourth arc), the lanes
+// are the batch's sources, so a slot is written by one lane group.  The order of the additions is that of
+// grx_edge_sum.h: a fixed tree over each aligned group of 16 consecutive sources, the groups one after another in
+// source order -- the same bits for S = 16, 32 and 64.  The unused lanes of a partial batch have no path (depth -2) and
+// hold +0.0.  Undirected: the edge is the sum of its two arc slots (grx_edge_sum.h's final passes, with the scale).
 #pragma clang fp contract(off)
 
 #include "grx_relax.h"
+#include "grx_edge_sum.h"
 
 #include <algorithm>
 
@@ -61,34 +72,39 @@ constexpr size_t WB_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of 
 constexpr int32_t WB_OPEN = -1;                              // reached, depth not known yet
 constexpr int32_t WB_UNREACHED = -2;
 
-// D, delta, sigma (fp64) and depth (int32) per cell, the relaxation's stamp per node
-size_t state_bytes(int64_t n, int S) { return (size_t)(n > 0 ? n : 1) * ((size_t)S * 28 + 4); }
+// D, delta, sigma (fp64) and depth (int32) per cell, the relaxation's stamp per node; grx_weighted_edge_betweenness
+// keeps coeff (fp64) in an array of its own
+size_t state_bytes(int64_t n, int S, bool keep_sigma)
+{
+    return (size_t)(n > 0 ? n : 1) * ((size_t)S * (keep_sigma ? 36 : 28) + 4);
+}
 
 // batch = 0: the widest S whose state fits WB_DEFAULT_STATE_BYTES, never below 16 and no wider than the source list
 // rounded up
-int choose_batch(int64_t n, int batch, int64_t n_sources)
+int choose_batch(int64_t n, int batch, int64_t n_sources, bool keep_sigma = false)
 {
     if (batch > 0) return batch;
     int widest = 16;
-    while (widest < 64 && state_bytes(n, widest * 2) <= WB_DEFAULT_STATE_BYTES) widest *= 2;
+    while (widest < 64 && state_bytes(n, widest * 2, keep_sigma) <= WB_DEFAULT_STATE_BYTES) widest *= 2;
     int s = 16;
     while (s < widest && s < n_sources) s *= 2;
     return s;
 }
 
-size_t ws_bytes(int64_t n, int S)
+size_t ws_bytes(int64_t n, int S, bool keep_sigma = false)
 {
     const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)S;
-    return 3 * grx_align_up(cells * 8, 256) + grx_align_up(cells * 4, 256) +
+    return (keep_sigma ? 4 : 3) * grx_align_up(cells * 8, 256) + grx_align_up(cells * 4, 256) +
            grx_align_up((size_t)(n > 0 ? n : 1) * 4, 256) + 256 + 256;
 }
 
 struct WbWs {
     double *D, *delta, *sigma;
+    double *coeff;                                           // the edge entry point only; otherwise coeff replaces sigma
     int32_t *depth, *stamp, *reach, *ctrl;
 };
 
-WbWs carve(void *base, int64_t n, int S)
+WbWs carve(void *base, int64_t n, int S, bool keep_sigma = false)
 {
     const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)S;
     char *p = reinterpret_cast<char *>(base);
@@ -96,6 +112,8 @@ WbWs carve(void *base, int64_t n, int S)
     ws.D = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
     ws.delta = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
     ws.sigma = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
+    ws.coeff = nullptr;
+    if (keep_sigma) { ws.coeff = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256); }
     ws.depth = reinterpret_cast<int32_t *>(p); p += grx_align_up(cells * 4, 256);
     ws.stamp = reinterpret_cast<int32_t *>(p); p += grx_align_up((size_t)(n > 0 ? n : 1) * 4, 256);
     ws.reach = reinterpret_cast<int32_t *>(p); p += 256;
@@ -284,22 +302,24 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_reach_kernel(int64_t n, const int
 }
 
 // networkx _accumulate_*: coeff = (1 + delta[w]) / sigma[w]; delta[v] += sigma[v] * coeff
-__device__ __forceinline__ void settle(int64_t cell, double d, double sv, double *sigma, double *__restrict__ delta)
+__device__ __forceinline__ void settle(int64_t cell, double d, double sv, double *coeff, double *__restrict__ delta)
 {
     delta[cell] = d;
-    sigma[cell] = (1.0 + d) / sv;                            // coeff(v) for the shallower levels
+    coeff[cell] = (1.0 + d) / sv;                            // coeff(v) for the shallower levels
 }
 
-// backward, level l: the cells at depth l pull delta from their DAG successors
-template <int S>
+// backward, level l: the cells at depth l pull delta from their DAG successors.  KEEP_SIGMA = false: coeff replaces
+// sigma in place (kept_coeff is not read); true: coeff goes to kept_coeff
+template <int S, bool KEEP_SIGMA>
 __global__ __launch_bounds__(WB_BLOCK) void wb_backward_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
                                                                const int32_t *__restrict__ col,
                                                                const double *__restrict__ w, int64_t hub_degree, int l,
                                                                const double *__restrict__ D,
                                                                const int32_t *__restrict__ depth, double *sigma,
-                                                               double *__restrict__ delta)
+                                                               double *kept_coeff, double *__restrict__ delta)
 {
     constexpr int GROUPS = WB_BLOCK / S;
+    double *coeff = KEEP_SIGMA ? kept_coeff : sigma;
     const int lane = threadIdx.x % S;
     for (int64_t v = (int64_t)blockIdx.x * GROUPS + threadIdx.x / S; v < n; v += (int64_t)gridDim.x * GROUPS) {
         const int64_t cell = v * S + lane;
@@ -307,32 +327,34 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_backward_kernel(int64_t n, const 
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
         if (e - b > hub_degree) continue;                   // wb_backward_hub_kernel
         const double sv = sigma[cell];
-        settle(cell, pull_succ<S>(b, e, 1, col, w, D, depth, sigma, lane, D[cell], l, sv), sv, sigma, delta);
+        settle(cell, pull_succ<S>(b, e, 1, col, w, D, depth, coeff, lane, D[cell], l, sv), sv, coeff, delta);
     }
 }
 
-template <int S>
+template <int S, bool KEEP_SIGMA>
 __global__ __launch_bounds__(WB_PARTS * S) void wb_backward_hub_kernel(const int64_t *__restrict__ row_ptr,
                                                                        const int32_t *__restrict__ col,
                                                                        const double *__restrict__ w,
                                                                        const int32_t *__restrict__ hub_rows, int l,
                                                                        const double *__restrict__ D,
                                                                        const int32_t *__restrict__ depth,
-                                                                       double *sigma, double *__restrict__ delta)
+                                                                       double *sigma, double *kept_coeff,
+                                                                       double *__restrict__ delta)
 {
     __shared__ double part[WB_PARTS][S];
+    double *coeff = KEEP_SIGMA ? kept_coeff : sigma;
     const int lane = threadIdx.x % S, p = threadIdx.x / S;
     const int64_t v = hub_rows[blockIdx.x];
     const int64_t cell = v * S + lane;
     const bool mine = depth[cell] == l;
     if (!__syncthreads_or(mine)) return;
     const double sv = mine ? sigma[cell] : 1.0;
-    part[p][lane] = mine ? pull_succ<S>(row_ptr[v] + p, row_ptr[v + 1], WB_PARTS, col, w, D, depth, sigma, lane,
+    part[p][lane] = mine ? pull_succ<S>(row_ptr[v] + p, row_ptr[v + 1], WB_PARTS, col, w, D, depth, coeff, lane,
                                         D[cell], l, sv)
                          : 0.0;
     __syncthreads();
     if (p != 0 || !mine) return;
-    settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, sigma, delta);
+    settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, coeff, delta);
 }
 
 // bc[v] += the contributions of the batch's sources in lane order (networkx: betweenness[w] += delta[w] for w != s;
@@ -363,16 +385,84 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_scale_kernel(int64_t n, double sc
         bc[v] *= scale;
 }
 
+// grx_weighted_edge_betweenness, after the backward loop of a batch: the arcs [b, e) with stride `step` of row v, the
+// S lanes of the group (it starts at wavefront lane `base`) being the batch's sources.  A lane holds sigma(v) *
+// coeff(x) when v -> x is an arc of its source's DAG -- v resolved, x deeper, and the tight-arc test of pull_succ --
+// and +0.0 otherwise; grx_edge_sum.h's order adds them onto the slot, which the group's first lane reads and writes.
+template <int S>
+__device__ __forceinline__ void edge_row(int64_t v, int64_t b, int64_t e, int step, const int32_t *__restrict__ col,
+                                         const double *__restrict__ w, const double *__restrict__ D,
+                                         const int32_t *__restrict__ depth, const double *__restrict__ sigma,
+                                         const double *__restrict__ coeff, int lane, int base,
+                                         double *__restrict__ ebc)
+{
+    const int pv = depth[v * S + lane];
+    if (!eb_group_any<S>(pv >= 0, base)) return;            // the same in every lane of the group
+    const double dv = D[v * S + lane];
+    const double sv = pv >= 0 ? sigma[v * S + lane] : 0.0;
+    for (int64_t j = b; j < e; j += step) {
+        const int64_t x = col[j];
+        bool on = pv >= 0 && depth[x * S + lane] > pv;
+        if (on) {
+            const double dx = D[x * S + lane];
+            on = dv + (w ? w[j] : 1.0) == dx && dv < dx;
+        }
+        if (!eb_group_any<S>(on, base)) continue;           // S times +0.0
+        const double acc = eb_add_groups<S>(lane == 0 ? ebc[j] : 0.0, on ? sv * coeff[x * S + lane] : 0.0, base);
+        if (lane == 0) ebc[j] = acc;
+    }
+}
+
+// rows up to hub_degree arcs: S lanes per row, WB_BLOCK / S rows per workgroup and grid step
+template <int S>
+__global__ __launch_bounds__(WB_BLOCK) void wb_edge_kernel(int64_t n, const int64_t *__restrict__ row_ptr,
+                                                           const int32_t *__restrict__ col,
+                                                           const double *__restrict__ w, int64_t hub_degree,
+                                                           const double *__restrict__ D,
+                                                           const int32_t *__restrict__ depth,
+                                                           const double *__restrict__ sigma,
+                                                           const double *__restrict__ coeff, double *__restrict__ ebc)
+{
+    constexpr int GROUPS = WB_BLOCK / S;
+    const int lane = threadIdx.x % S;
+    const int base = threadIdx.x % GRX_WAVE - lane;
+    for (int64_t v = (int64_t)blockIdx.x * GROUPS + threadIdx.x / S; v < n; v += (int64_t)gridDim.x * GROUPS) {
+        const int64_t b = row_ptr[v], e = row_ptr[v + 1];
+        if (e - b > hub_degree) continue;                   // wb_edge_hub_kernel
+        edge_row<S>(v, b, e, 1, col, w, D, depth, sigma, coeff, lane, base, ebc);
+    }
+}
+
+// hub rows: one workgroup of WB_PARTS * S threads per hub row; part p takes every WB_PARTS-th arc (a slot still has
+// one owner)
+template <int S>
+__global__ __launch_bounds__(WB_PARTS * S) void wb_edge_hub_kernel(const int64_t *__restrict__ row_ptr,
+                                                                   const int32_t *__restrict__ col,
+                                                                   const double *__restrict__ w,
+                                                                   const int32_t *__restrict__ hub_rows,
+                                                                   const double *__restrict__ D,
+                                                                   const int32_t *__restrict__ depth,
+                                                                   const double *__restrict__ sigma,
+                                                                   const double *__restrict__ coeff,
+                                                                   double *__restrict__ ebc)
+{
+    const int lane = threadIdx.x % S, p = threadIdx.x / S;
+    const int base = threadIdx.x % GRX_WAVE - lane;
+    const int64_t v = hub_rows[blockIdx.x];
+    edge_row<S>(v, row_ptr[v] + p, row_ptr[v + 1], WB_PARTS, col, w, D, depth, sigma, coeff, lane, base, ebc);
+}
+
 struct Args {
     int64_t n;
     SpPull out, in;                                          // backward pulls over `out`; relaxation and forward over `in`
     const int32_t *sources;
     int64_t n_sources;
     int endpoints;
-    double *bc;
+    double *bc;                                              // EDGES: ebc, one value per arc of `out`
 };
 
-template <int S>
+// EDGES = false is grx_weighted_betweenness, true is grx_weighted_edge_betweenness (`endpoints` is 0 there)
+template <int S, bool EDGES>
 int run(const Args &a, const WbWs &ws, int64_t *rounds, int64_t *levels, hipStream_t st)
 {
     const int64_t n = a.n, cells = n * S;
@@ -382,7 +472,9 @@ int run(const Args &a, const WbWs &ws, int64_t *rounds, int64_t *levels, hipStre
         const int count = (int)std::min<int64_t>(S, a.n_sources - first);
         int rc = sp_relax<S>(
             a.in, a.sources + first, count, ws.D, ws.delta, ws.stamp, ws.ctrl,
-            "grx_weighted_betweenness: the relaxation did not end after %lld rounds (a negative or NaN weight?)",
+            EDGES ? "grx_weighted_edge_betweenness: the relaxation did not end after %lld rounds (a negative or NaN "
+                    "weight?)"
+                  : "grx_weighted_betweenness: the relaxation did not end after %lld rounds (a negative or NaN weight?)",
             GRX_K_WBC_RELAX, rounds, st);
         if (rc != GRX_OK) return rc;
         // both distance buffers hold the fixed point: ws.delta is free
@@ -393,8 +485,9 @@ int run(const Args &a, const WbWs &ws, int64_t *rounds, int64_t *levels, hipStre
         int32_t h[2];
         // a DAG over n nodes is at most n - 1 arcs deep; one more round finds that nothing resolves
         rc = grx_run_rounds(
-            "grx_weighted_betweenness: the forward pass did not end after %lld rounds", WB_LEVEL_BATCH, n + 1, 2,
-            ws.ctrl, h, st, [&] {
+            EDGES ? "grx_weighted_edge_betweenness: the forward pass did not end after %lld rounds"
+                  : "grx_weighted_betweenness: the forward pass did not end after %lld rounds",
+            WB_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
                 GRX_PROF(GRX_K_WBC_FORWARD, st);
                 if (a.in.n_hub_rows)
                     wb_forward_hub_kernel<S><<<(unsigned)a.in.n_hub_rows, WB_PARTS * S, 0, st>>>(
@@ -411,16 +504,82 @@ int run(const Args &a, const WbWs &ws, int64_t *rounds, int64_t *levels, hipStre
         for (int l = h[GRX_CT_LEVEL]; l >= 1; --l) {        // deepest level first; the sources need no delta
             GRX_PROF(GRX_K_WBC_BACKWARD, st);
             if (a.out.n_hub_rows)
-                wb_backward_hub_kernel<S><<<(unsigned)a.out.n_hub_rows, WB_PARTS * S, 0, st>>>(
-                    a.out.row_ptr, a.out.col, a.out.w, a.out.hub_rows, l, ws.D, ws.depth, ws.sigma, ws.delta);
-            wb_backward_kernel<S><<<row_blocks, WB_BLOCK, 0, st>>>(n, a.out.row_ptr, a.out.col, a.out.w,
-                                                                   a.out.hub_degree, l, ws.D, ws.depth, ws.sigma,
-                                                                   ws.delta);
+                wb_backward_hub_kernel<S, EDGES><<<(unsigned)a.out.n_hub_rows, WB_PARTS * S, 0, st>>>(
+                    a.out.row_ptr, a.out.col, a.out.w, a.out.hub_rows, l, ws.D, ws.depth, ws.sigma, ws.coeff, ws.delta);
+            wb_backward_kernel<S, EDGES><<<row_blocks, WB_BLOCK, 0, st>>>(n, a.out.row_ptr, a.out.col, a.out.w,
+                                                                          a.out.hub_degree, l, ws.D, ws.depth, ws.sigma,
+                                                                          ws.coeff, ws.delta);
             GRX_LAUNCH_CHECK();
         }
-        wb_accumulate_kernel<S><<<egrid, WB_BLOCK, 0, st>>>(n, count, a.endpoints, ws.depth, ws.delta, ws.reach, a.bc);
+        if (EDGES) {
+            if (a.out.n_hub_rows)
+                wb_edge_hub_kernel<S><<<(unsigned)a.out.n_hub_rows, WB_PARTS * S, 0, st>>>(
+                    a.out.row_ptr, a.out.col, a.out.w, a.out.hub_rows, ws.D, ws.depth, ws.sigma, ws.coeff, a.bc);
+            wb_edge_kernel<S><<<row_blocks, WB_BLOCK, 0, st>>>(n, a.out.row_ptr, a.out.col, a.out.w, a.out.hub_degree,
+                                                               ws.D, ws.depth, ws.sigma, ws.coeff, a.bc);
+        } else {
+            wb_accumulate_kernel<S><<<egrid, WB_BLOCK, 0, st>>>(n, count, a.endpoints, ws.depth, ws.delta, ws.reach,
+                                                                a.bc);
+        }
         GRX_LAUNCH_CHECK();
     }
+    return GRX_OK;
+}
+
+// the argument checks and the batches of both entry points
+template <bool EDGES>
+int entry(const char *name, int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
+          const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr,
+          const int32_t *d_in_col, const double *d_in_w, const int32_t *d_in_hub_rows, int64_t n_in_hub_rows,
+          int in_lanes_per_row, const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch,
+          double *d_out, int64_t *h_rounds, int64_t *h_levels, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    GRX_REQUIRE(batch == 0 || sp_valid_batch(batch), "%s: batch must be 0, 16, 32 or 64 (got %d)", name, batch);
+    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "%s: n = %lld out of range", name, (long long)n);
+    GRX_REQUIRE(d_row_ptr && d_col && d_out && d_workspace, "%s: null pointer", name);
+    GRX_REQUIRE(n_sources >= 0 && n_sources < (int64_t)1 << 31 && (n_sources == 0 || d_sources), "%s: source list",
+                name);
+    const bool directed = d_in_row_ptr != nullptr;
+    GRX_REQUIRE(!directed || d_in_col, "%s: d_in_col is required with d_in_row_ptr", name);
+    GRX_REQUIRE(!directed || (d_w == nullptr) == (d_in_w == nullptr),
+                "%s: d_w and d_in_w must both be given or both be NULL", name);
+    if (!directed) {                                         // undirected: the CSR is its own in-adjacency
+        d_in_row_ptr = d_row_ptr;
+        d_in_col = d_col;
+        d_in_w = d_w;
+        d_in_hub_rows = d_hub_rows;
+        n_in_hub_rows = n_hub_rows;
+        in_lanes_per_row = lanes_per_row;
+    }
+    GRX_REQUIRE(lanes_per_row >= 1 && in_lanes_per_row >= 1, "%s: lanes_per_row must be >= 1", name);
+    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows) && n_in_hub_rows >= 0 &&
+                    (n_in_hub_rows == 0 || d_in_hub_rows), "%s: hub list", name);
+    const int S = choose_batch(n, batch, n_sources, EDGES);
+    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, S, EDGES), "%s: workspace %zu bytes, need %zu", name, workspace_bytes,
+                ws_bytes(n, S, EDGES));
+    hipStream_t st = grx_stream(stream);
+    const WbWs ws = carve(d_workspace, n, S, EDGES);
+    const Args a{n,
+                 SpPull{n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row},
+                 SpPull{n, d_in_row_ptr, d_in_col, d_in_w, d_in_hub_rows, n_in_hub_rows,
+                        (int64_t)GRX_HUB_FACTOR * in_lanes_per_row},
+                 d_sources, n_sources, endpoints, d_out};
+    if (EDGES) eb_rows<EB_ZERO>(n, d_row_ptr, d_col, 0.0, d_out, st);
+    else grx_fill64(reinterpret_cast<uint64_t *>(d_out), n, 0, st);
+    GRX_LAUNCH_CHECK();
+    int64_t rounds = 0, levels = 0;
+    int rc;
+    switch (S) {
+    case 16: rc = run<16, EDGES>(a, ws, &rounds, &levels, st); break;
+    case 32: rc = run<32, EDGES>(a, ws, &rounds, &levels, st); break;
+    default: rc = run<64, EDGES>(a, ws, &rounds, &levels, st); break;
+    }
+    if (h_rounds) *h_rounds = rounds;
+    if (h_levels) *h_levels = levels;
+    if (rc != GRX_OK) return rc;
+    if (EDGES) eb_finish(n, d_row_ptr, d_col, directed, scale, d_out, st);
+    else wb_scale_kernel<<<grx_grid(n, WB_BLOCK, WB_MAX_BLOCKS), WB_BLOCK, 0, st>>>(n, scale, d_out);
+    GRX_LAUNCH_CHECK();
     return GRX_OK;
 }
 
@@ -441,52 +600,29 @@ int grx_weighted_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t 
                              double *d_bc, int64_t *h_rounds, int64_t *h_levels, void *d_workspace,
                              size_t workspace_bytes, void *stream)
 {
-    GRX_REQUIRE(batch == 0 || sp_valid_batch(batch), "grx_weighted_betweenness: batch must be 0, 16, 32 or 64 (got %d)",
-                batch);
-    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "grx_weighted_betweenness: n = %lld out of range", (long long)n);
-    GRX_REQUIRE(d_row_ptr && d_col && d_bc && d_workspace, "grx_weighted_betweenness: null pointer");
-    GRX_REQUIRE(n_sources >= 0 && n_sources < (int64_t)1 << 31 && (n_sources == 0 || d_sources),
-                "grx_weighted_betweenness: source list");
-    const bool directed = d_in_row_ptr != nullptr;
-    GRX_REQUIRE(!directed || d_in_col, "grx_weighted_betweenness: d_in_col is required with d_in_row_ptr");
-    GRX_REQUIRE(!directed || (d_w == nullptr) == (d_in_w == nullptr),
-                "grx_weighted_betweenness: d_w and d_in_w must both be given or both be NULL");
-    if (!directed) {                                         // undirected: the CSR is its own in-adjacency
-        d_in_row_ptr = d_row_ptr;
-        d_in_col = d_col;
-        d_in_w = d_w;
-        d_in_hub_rows = d_hub_rows;
-        n_in_hub_rows = n_hub_rows;
-        in_lanes_per_row = lanes_per_row;
-    }
-    GRX_REQUIRE(lanes_per_row >= 1 && in_lanes_per_row >= 1, "grx_weighted_betweenness: lanes_per_row must be >= 1");
-    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows) && n_in_hub_rows >= 0 &&
-                    (n_in_hub_rows == 0 || d_in_hub_rows), "grx_weighted_betweenness: hub list");
-    const int S = choose_batch(n, batch, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, S), "grx_weighted_betweenness: workspace %zu bytes, need %zu",
-                workspace_bytes, ws_bytes(n, S));
-    hipStream_t st = grx_stream(stream);
-    const WbWs ws = carve(d_workspace, n, S);
-    const Args a{n,
-                 SpPull{n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row},
-                 SpPull{n, d_in_row_ptr, d_in_col, d_in_w, d_in_hub_rows, n_in_hub_rows,
-                        (int64_t)GRX_HUB_FACTOR * in_lanes_per_row},
-                 d_sources, n_sources, endpoints, d_bc};
-    grx_fill64(reinterpret_cast<uint64_t *>(d_bc), n, 0, st);
-    GRX_LAUNCH_CHECK();
-    int64_t rounds = 0, levels = 0;
-    int rc;
-    switch (S) {
-    case 16: rc = run<16>(a, ws, &rounds, &levels, st); break;
-    case 32: rc = run<32>(a, ws, &rounds, &levels, st); break;
-    default: rc = run<64>(a, ws, &rounds, &levels, st); break;
-    }
-    if (h_rounds) *h_rounds = rounds;
-    if (h_levels) *h_levels = levels;
-    if (rc != GRX_OK) return rc;
-    wb_scale_kernel<<<grx_grid(n, WB_BLOCK, WB_MAX_BLOCKS), WB_BLOCK, 0, st>>>(n, scale, d_bc);
-    GRX_LAUNCH_CHECK();
-    return GRX_OK;
+    return entry<false>("grx_weighted_betweenness", n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows, lanes_per_row,
+                        d_in_row_ptr, d_in_col, d_in_w, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources,
+                        n_sources, endpoints, scale, batch, d_bc, h_rounds, h_levels, d_workspace, workspace_bytes,
+                        stream);
+}
+
+size_t grx_weighted_edge_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources)
+{
+    return ws_bytes(n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources, true), true);
+}
+
+int grx_weighted_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
+                                  const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                                  const int64_t *d_in_row_ptr, const int32_t *d_in_col, const double *d_in_w,
+                                  const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
+                                  const int32_t *d_sources, int64_t n_sources, double scale, int batch, double *d_ebc,
+                                  int64_t *h_rounds, int64_t *h_levels, void *d_workspace, size_t workspace_bytes,
+                                  void *stream)
+{
+    return entry<true>("grx_weighted_edge_betweenness", n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows,
+                       lanes_per_row, d_in_row_ptr, d_in_col, d_in_w, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row,
+                       d_sources, n_sources, 0, scale, batch, d_ebc, h_rounds, h_levels, d_workspace, workspace_bytes,
+                       stream);
 }
 
 }  // extern "C"

@@ -40,6 +40,11 @@ SP_MAX_BLOCKS = 2048         # csrc/grx_sssp.hip: workgroups of its per-node lau
 WB_BLOCK = 256               # csrc/grx_weighted_betweenness.hip: threads per workgroup,
 WB_MAX_ROW_BLOCKS = 8192     # workgroups of the row kernels (256 / batch rows each)
 WB_MAX_BLOCKS = 2048         # and of the per-element launches
+BW_BLOCK = 256               # csrc/grx_betweenness.hip: threads per workgroup,
+BW_MAX_ROW_BLOCKS = 1024     # workgroups of the row kernels (4 rows each: one wavefront per row), the edge pass among them
+EB_BLOCK = 256               # csrc/grx_edge_sum.h (grx_edge_betweenness, grx_weighted_edge_betweenness): threads per
+EB_ROW_LANES = 16            # workgroup and lanes per row of the passes that zero and finish the arc slots,
+EB_MAX_ROW_BLOCKS = 2048     # and their workgroups (256 / 16 rows each)
 CL_BLOCK = 256               # csrc/grx_closeness.hip (grx_distance_sums, grx_eccentricity): threads per workgroup
 CL_MAX_ROW_BLOCKS = 8192     # and workgroups of the level kernels (256 / words rows each)
 NS_BLOCK = 256               # csrc/grx_neighbor_sense.hip: threads per workgroup,
@@ -1397,6 +1402,37 @@ def weighted_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], source
               len(src), int(bool(endpoints)), float(scale), int(batch), _ptr(bc), ctypes.byref(rounds),
               ctypes.byref(levels), _ptr(ws), ws_bytes, _stream())
     return bc, int(rounds.value), int(levels.value)
+
+
+def edge_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.ndarray, scale: float,
+                     batch: int = 0) -> torch.Tensor:
+    """grx_edge_betweenness: unweighted edge betweenness from `sources` (internal row ids, in accumulation order) over
+    the out-adjacency csr_out and the in-adjacency csr_in (None for an undirected graph): fp64[nnz], one value per arc
+    of csr_out, multiplied by `scale`; both arcs of an undirected edge hold the edge's value.  batch = sources per batch
+    (a multiple of 64; 0 = the library's choice)."""
+    n = csr_out.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    ws, ws_bytes = _workspace('grx_edge_betweenness_workspace_bytes', n, int(batch), len(src))
+    ebc = torch.empty(max(csr_out.nnz, 1), dtype=torch.float64, device=device())
+    _lib.call('grx_edge_betweenness', n, *_csr_args(csr_out), *_csr_args(csr_in), _ptr(src), len(src), float(scale),
+              int(batch), _ptr(ebc), _ptr(ws), ws_bytes, _stream())
+    return ebc
+
+
+def weighted_edge_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.ndarray, scale: float,
+                              batch: int = 0) -> Tuple[torch.Tensor, int, int]:
+    """grx_weighted_edge_betweenness: edge betweenness over shortest paths by arc weight, arguments as
+    ``weighted_betweenness`` without `endpoints`.  (ebc fp64[nnz] as ``edge_betweenness``, relaxation rounds summed
+    over the batches, the deepest level of the shortest-path DAG).  batch = 16, 32 or 64; 0 = the library's choice."""
+    n = csr_out.n
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    ws, ws_bytes = _workspace('grx_weighted_edge_betweenness_workspace_bytes', n, int(batch), len(src))
+    ebc = torch.empty(max(csr_out.nnz, 1), dtype=torch.float64, device=device())
+    rounds, levels = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call('grx_weighted_edge_betweenness', n, *_weighted_csr_args(csr_out), *_weighted_csr_args(csr_in), _ptr(src),
+              len(src), float(scale), int(batch), _ptr(ebc), ctypes.byref(rounds), ctypes.byref(levels), _ptr(ws),
+              ws_bytes, _stream())
+    return ebc, int(rounds.value), int(levels.value)
 
 
 def biconnected(csr: DeviceCSR, want_forest: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor],

@@ -38,7 +38,10 @@ one more per edge as the edges leave, all in integers, and -- with ``graphlet_de
 the graphlet degree vector of every node of a simple undirected graph (Przulj's orbits 0-14 of the graphs on 2, 3 and 4
 nodes, induced; there is no networkx function to restate: the authority is brute-force enumeration), by
 csrc/grx_graphlets.hip: non-induced counts from degrees, triangles per edge, the 4-cycles of the square-clustering
-kernel and a 4-clique listing on the degree-oriented graph, then an integer back-substitution.
+kernel and a 4-clique listing on the degree-oriented graph, then an integer back-substitution, and -- with
+``edge_betweenness_centrality`` -- the betweenness of every edge, by hops or by weight, as networkx's
+``edge_betweenness_centrality(G, k, normalized, weight, seed)`` defines it, by the two betweenness files with sigma kept
+and one pass per batch over the arcs of the shortest-path DAGs (csrc/grx_edge_sum.h states the order of its sums).
 """
 from __future__ import annotations
 
@@ -488,6 +491,106 @@ def weighted_betweenness_centrality(G, k: Optional[int] = None, normalized: bool
                           betweenness_weight='weight')
     series = frame['betweenness_centrality']
     series.attrs = dict(frame.attrs['weighted_betweenness'])
+    return series
+
+
+def _rescale_e_factor(n: int, normalized: bool, directed: bool) -> float:
+    """The factor of networkx 3.4.2's _rescale_e as edge_betweenness_centrality calls it -- without `k`, so a sampled
+    run is not multiplied by n / k (1.0 where networkx leaves the sums as they are)."""
+    if normalized:
+        return 1.0 if n <= 1 else 1 / (n * (n - 1))
+    return 1.0 if directed else 0.5
+
+
+def _edge_series(graph, u: np.ndarray, v: np.ndarray, values: np.ndarray, name: str) -> pd.Series:
+    """Series of one value per (u, v) -- rows of the sorted labels -- behind the two-level MultiIndex of
+    ``truss_number``, in lexicographic order."""
+    order = np.lexsort((v, u))
+    u, v = u[order], v[order]
+    labels = _label_index(graph)
+    if isinstance(labels, pd.MultiIndex):                       # tuple labels: each level holds the tuples themselves
+        held = np.empty(len(labels), dtype=object)
+        held[:] = list(labels)
+        ends = [held[u], held[v]]
+    else:
+        ends = [labels.take(u), labels.take(v)]
+    return pd.Series(values[order], name=name, index=pd.MultiIndex.from_arrays(ends, names=['u', 'v']))
+
+
+def edge_betweenness_centrality(G, k: Optional[int] = None, normalized: bool = True, weight=None,
+                                seed=None) -> pd.Series:
+    """
+    Edge betweenness centrality on the GPU: networkx 3.4.2's ``edge_betweenness_centrality(G, k, normalized, weight,
+    seed)`` -- the share of the shortest paths that run over an edge, the quantity Girvan-Newman removes edges by.
+    Next to ``truss_number`` (how embedded a tie is) it says how much traffic the tie carries: truss number 2 with a
+    high value is a bridge between groups, a high truss number with a low value a redundant tie inside one.  The
+    forward and backward passes are those of ``betweenness_centrality`` (csrc/grx_betweenness.hip) resp.
+    ``weighted_betweenness_centrality`` (csrc/grx_weighted_betweenness.hip) with sigma kept; one more pass per batch
+    adds networkx's own term ``sigma[v] * coeff(w)`` of ``_accumulate_edges`` onto every arc of a source's
+    shortest-path DAG.
+
+    :param G: any graph ``node_measures`` accepts, without parallel edges
+    :param k, seed: as ``betweenness_centrality``: the same sources in the same order
+    :param normalized: as networkx.  The scale is that of networkx 3.4.2 AS IT IS: ``edge_betweenness_centrality`` calls
+      ``_rescale_e(betweenness, len(G), normalized=..., directed=...)`` without passing `k`, so a sampled run is NOT
+      multiplied by n / k: 1 / (n (n - 1)) when normalized and n > 1, otherwise 0.5 for an undirected graph and
+      nothing for a directed one
+    :param weight: None = shortest paths by hops; ``'weight'`` = by the edge attribute the adapters read (a missing
+      attribute counts 1)
+    :return: float64 Series named ``edge_betweenness_centrality`` behind a two-level MultiIndex (levels ``u``, ``v``) of
+      node labels, rows in lexicographic order of the sorted labels.  Undirected: one row per edge with u before v,
+      self-loops included at 0.0 (networkx keeps them as keys); directed: one row per arc u -> v.  With a weight
+      ``.attrs['rounds']`` and ``.attrs['levels']`` as ``weighted_betweenness_centrality``
+    :raises NotImplementedError: a multigraph or parallel edges (networkx splits the value between parallel edges: a
+      stated divergence); another `weight`; G is directed and its adapter has no in-adjacency
+    :raises ValueError: k outside 1..n; with a weight, a weight that is not finite and > 0
+    :raises TypeError: a seed of another type
+
+    Values agree with networkx to 1e-12 relative (only the order of additions differs) and the entries networkx has at
+    exactly 0 are exactly 0; the same bits for every batch width and run.  An empty graph or one without edges returns
+    the empty Series without device work.  The name is not in ``CATALOGUE``: edges are not rows of the node table.
+    """
+    name = 'edge_betweenness_centrality'
+    graph = _adapter(G)
+    weighted = _weight_flag(name, weight)
+    what = f"edge_betweenness_centrality(G, weight={weight!r})"
+    if _has_parallel_edges(graph):
+        raise NotImplementedError(f'{what}: not computed on a multigraph or a graph with parallel edges (networkx '
+                                  f'splits the value of an arc between its parallel edges); merge them first')
+    sources = _betweenness_sources(graph, k, seed)              # argument errors before any device work
+    if weighted:
+        _weighted_betweenness_refusals(graph, what)
+    g = graph.to_csr()
+    directed = bool(graph.directed)
+    if g.n == 0 or g.num_edges == 0:
+        series = pd.Series(np.zeros(0), name=name, index=pd.MultiIndex.from_arrays([[], []], names=['u', 'v']))
+        if weighted:
+            series.attrs.update(rounds=0, levels=0)
+        return series
+    K = graph._K()
+    scale = _rescale_e_factor(g.n, normalized, directed)
+    if weighted:
+        host, out, tr = graph._device_graph()
+        if directed:
+            _weighted_pull(graph, 'weighted edge betweenness centrality')
+    else:
+        host = graph._device_graph()[0]
+        out, tr = _structure_pair(graph, name)
+    rows = np.asarray(host.inv)[sources]
+    if weighted:
+        ebc, rounds, levels = K.weighted_edge_betweenness(out, tr if directed else None, rows, scale)
+    else:
+        ebc = K.edge_betweenness(out, tr if directed else None, rows, scale)
+    row_ptr = np.asarray(_row_ptr_of(K, out), dtype=np.int64)
+    nnz = int(row_ptr[-1])
+    perm = np.asarray(host.perm, dtype=np.int64)                # internal row -> row of the sorted labels
+    u = perm[np.repeat(np.arange(host.n, dtype=np.int64), np.diff(row_ptr))]
+    v = perm[_on_host(K, out.col)[:nnz].astype(np.int64)]
+    values = _on_host(K, ebc)[:nnz].astype(np.float64)
+    keep = np.arange(nnz) if directed else np.nonzero(u <= v)[0]   # undirected: both arcs hold the edge's value
+    series = _edge_series(graph, u[keep], v[keep], values[keep], name)
+    if weighted:
+        series.attrs.update(rounds=rounds, levels=levels)
     return series
 
 

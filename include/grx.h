@@ -39,7 +39,8 @@ extern "C" {
                                     so did grx_graphlet_orbits (graphlet degree vectors, orbits 0-14) and
                                     grx_neighbor_roles (the neighbour-role table of NeighborSense) and
                                     grx_similar_rows (structural similarity: exact top-k nearest rows) and
-                                    grx_components / grx_reachable (connected, weak and strong components, closures)
+                                    grx_components / grx_reachable (connected, weak and strong components, closures) and
+                                    grx_edge_betweenness / grx_weighted_edge_betweenness (edge betweenness centrality)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1021,6 +1022,54 @@ int grx_weighted_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t 
                              const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch,
                              double *d_bc, int64_t *h_rounds, int64_t *h_levels, void *d_workspace,
                              size_t workspace_bytes, void *stream);
+
+/*
+ * grx_edge_betweenness restates networkx.edge_betweenness_centrality(G, k, normalized, weight=None, seed) (betweenness.py:
+ *   edge_betweenness_centrality, _single_source_shortest_path_basic, _accumulate_edges, _rescale_e) for the sources
+ *   d_sources[0 .. n_sources) in that order: the forward and backward passes of grx_betweenness (same kernels, same
+ *   arguments without `endpoints`) with coeff kept in an array of its own, so that sigma survives; then, per batch, the
+ *   slot of every arc v -> w of a source's BFS DAG (level(w) == level(v) + 1) adds c = sigma(v) * coeff(w), networkx's
+ *   own term of _accumulate_edges.  d_ebc: fp64, one value per arc of the out CSR (d_row_ptr / d_col), overwritten.
+ *   Directed (d_in_row_ptr given): the slot of u -> v is the arc's sum times scale.  Undirected: networkx keeps one key
+ *   per edge; for one source only one of its two arcs is a DAG arc, so the edge is (slot(u -> v) + slot(v -> u)) *
+ *   scale, and BOTH slots of the edge hold that value at the end (the mirror slot is found by binary search in the
+ *   sorted row; the rows must be sorted and the CSR symmetric).  Self-loop slots are exactly 0.0.  scale: the caller
+ *   computes _rescale_e's factor, 1 for none (networkx 3.4.2 does not pass k to _rescale_e: no n / k for sampled
+ *   sources).  batch: as grx_betweenness, with 28 n B bytes of state (level, sigma, delta, coeff).
+ *   ORDER of the additions into a slot: the source list is cut into aligned groups of 16 consecutive sources; a group's
+ *   16 terms (+0.0 where the arc is no DAG arc of the source or the list has ended) are summed by the fixed pairwise
+ *   tree (((t0 + t1) + (t2 + t3)) + ...), and the group sums are added one after another in source order onto the slot.
+ *   That depends on a source's position in d_sources alone: the same bits for every B, launch shape and run; no
+ *   floating-point atomics (one wavefront owns a slot).  Against networkx only the order in which a slot adds its
+ *   sources and the order inside one delta(v) differ: 1e-12 relative; values networkx has at exactly 0 are exactly 0.
+ *   d_workspace: grx_edge_betweenness_workspace_bytes(n, batch, n_sources) bytes.  Errors as grx_betweenness.
+ */
+size_t grx_edge_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources);
+int grx_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+                         int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+                         const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
+                         const int32_t *d_sources, int64_t n_sources, double scale, int batch, double *d_ebc,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
+/*
+ * grx_weighted_edge_betweenness restates networkx.edge_betweenness_centrality(G, k, normalized, weight, seed) for a
+ *   weight attribute (betweenness.py: edge_betweenness_centrality, _single_source_dijkstra_path_basic,
+ *   _accumulate_edges, _rescale_e): the relaxation, forward and backward passes of grx_weighted_betweenness (same
+ *   kernels, same arguments without `endpoints`, same contract on the weights and the same stated divergences) with
+ *   coeff kept in an array of its own; then, per batch of S sources, the slot of every arc u -> v of a source's
+ *   shortest-path DAG (fl(D(u) + w) == D(v) and D(u) < D(v), u resolved, v deeper) adds sigma(u) * coeff(v).
+ *   d_ebc, directed / undirected slots, self-loops, scale, the ORDER of the additions and the tolerance against
+ *   networkx: as grx_edge_betweenness -- the same bits for S = 16, 32 and 64.  State: 36 n S + 4 n bytes.
+ *   h_rounds / h_levels: as grx_weighted_betweenness.
+ *   d_workspace: grx_weighted_edge_betweenness_workspace_bytes(n, batch, n_sources) bytes.
+ */
+size_t grx_weighted_edge_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources);
+int grx_weighted_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
+                                  const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
+                                  const int64_t *d_in_row_ptr, const int32_t *d_in_col, const double *d_in_w,
+                                  const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row,
+                                  const int32_t *d_sources, int64_t n_sources, double scale, int batch, double *d_ebc,
+                                  int64_t *h_rounds, int64_t *h_levels, void *d_workspace, size_t workspace_bytes,
+                                  void *stream);
 
 /*
  * grx_biconnected: for every node of an undirected graph the number of biconnected components it belongs to -- what
