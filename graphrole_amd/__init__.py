@@ -19,7 +19,7 @@ def __getattr__(name):
                 'effective_size', 'dijkstra_path_lengths', 'weighted_betweenness_centrality', 'clustering',
                 'average_clustering', 'square_clustering', 'truss_number', 'node_truss_number', 'k_truss',
                 'graphlet_degree_vectors', 'graphlet_counts', 'neighbor_roles', 'role_mixing_matrix',
-                'edge_betweenness_centrality', 'ConvergenceError'):
+                'edge_betweenness_centrality', 'triadic_census', 'node_triad_census', 'ConvergenceError'):
         from . import measures
         return getattr(measures, name)
     if name == 'nearest_nodes':

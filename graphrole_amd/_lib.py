@@ -296,7 +296,10 @@ _SIGNATURES = {
     'grx_graphlet_orbits_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'grx_graphlet_orbits': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'grx_neighbor_roles': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+    'grx_triad_census_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'grx_triad_census': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    'grx_neighbor_roles': (c_int,[c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                    c_void_p, c_int64, c_void_p]),
     'grx_similar_rows_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
     'grx_similar_rows': (c_int, [c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int,

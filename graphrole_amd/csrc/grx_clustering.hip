@@ -94,7 +94,7 @@ struct cl_arc {
     const double *__restrict__ s;
     double *__restrict__ term;
     struct Acc { double a; };
-    __device__ __forceinline__ bool begin(int32_t u, int32_t v, Acc &) const { return u != v; }
+    __device__ __forceinline__ bool begin(int64_t, int32_t u, int32_t v, Acc &) const { return u != v; }
     // u and v are tested at the hit: skipping their two searches up front splits the group before the search loop and
     // measured 6 % slower (profiles/clustering.txt)
     __device__ __forceinline__ void hit(int32_t u, int32_t v, int32_t w, int64_t k, int64_t lo, bool, Acc &a) const

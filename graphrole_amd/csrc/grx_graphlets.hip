@@ -110,7 +110,7 @@ struct gl_support {
     const int32_t *__restrict__ col, *__restrict__ arc_row;
     int32_t *__restrict__ rev, *__restrict__ sup;
     struct Acc { double c; };
-    __device__ __forceinline__ bool begin(int32_t u, int32_t v, Acc &) const { return u < v; }
+    __device__ __forceinline__ bool begin(int64_t, int32_t u, int32_t v, Acc &) const { return u < v; }
     __device__ __forceinline__ void hit(int32_t, int32_t, int32_t, int64_t, int64_t, bool, Acc &a) const { a.c += 1.0; }
     template <class R>
     __device__ __forceinline__ void reduce(Acc &a, R r) const { a.c = r.sum(a.c); }
@@ -192,7 +192,7 @@ struct gl_diamond {
     const int32_t *__restrict__ arc_row, *__restrict__ sup;
     unsigned long long *__restrict__ n12x2;
     struct Acc { double s; };
-    __device__ __forceinline__ bool begin(int32_t, int32_t, Acc &) const { return true; }
+    __device__ __forceinline__ bool begin(int64_t, int32_t, int32_t, Acc &) const { return true; }
     __device__ __forceinline__ void hit(int32_t, int32_t, int32_t, int64_t k, int64_t lo, bool walk_u, Acc &a) const
     {
         a.s += (double)(sup[walk_u ? lo : k] - 1);

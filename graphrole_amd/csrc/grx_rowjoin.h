@@ -19,7 +19,7 @@
 //                                                            lane of the group (thread of the workgroup) calls it
 //   void finish(int64_t u, int64_t b, int64_t e, const Acc &a) const;    lane 0 / thread 0; the row is [b, e)
 // and an arc body has the same Acc and reduce, and
-//   bool begin(int32_t u, int32_t v, Acc &a) const;          what the arc needs of u and v; false: no intersection
+//   bool begin(int64_t j, int32_t u, int32_t v, Acc &a) const;    what arc j needs of u and v; false: no intersection
 //   void hit(int32_t u, int32_t v, int32_t w, int64_t k, int64_t lo, bool walk_u, Acc &a) const;
 //                                                            w = col[k] = col[lo]: k in the walked row (u's if
 //                                                            walk_u), lo in the searched one
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(RJ_BLOCK) void rj_arc_kernel(int64_t nnz, const int
         typename Body::Acc a{};
         if (j < nnz) {
             const int32_t u = arc_row[j], v = col[j];
-            if (body.begin(u, v, a)) {
+            if (body.begin(j, u, v, a)) {
                 const int64_t bu = row_ptr[u], eu = row_ptr[u + 1], bv = row_ptr[v], ev = row_ptr[v + 1];
                 const bool walk_u = eu - bu <= ev - bv;     // walk the shorter row, search the longer one
                 const int64_t wb = walk_u ? bu : bv, we = walk_u ? eu : ev;

@@ -60,7 +60,7 @@ struct sh_arc {
     const double *__restrict__ z, *__restrict__ S, *__restrict__ X;
     double *__restrict__ loc, *__restrict__ red;
     struct Acc { double a, r, su, xv; };
-    __device__ __forceinline__ bool begin(int32_t u, int32_t v, Acc &a) const
+    __device__ __forceinline__ bool begin(int64_t, int32_t u, int32_t v, Acc &a) const
     {
         a.su = S[u];
         a.xv = X[v];

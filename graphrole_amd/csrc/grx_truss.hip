@@ -105,7 +105,7 @@ struct tr_support {                                          // (b) sup, rev and
     const int32_t *__restrict__ col, *__restrict__ arc_row;
     int32_t *__restrict__ rev, *__restrict__ sup, *__restrict__ state;
     struct Acc { double c; };                                // a count far below 2^53: exact
-    __device__ __forceinline__ bool begin(int32_t u, int32_t v, Acc &) const { return u < v; }
+    __device__ __forceinline__ bool begin(int64_t, int32_t u, int32_t v, Acc &) const { return u < v; }
     __device__ __forceinline__ void hit(int32_t, int32_t, int32_t, int64_t, int64_t, bool, Acc &a) const { a.c += 1.0; }
     template <class R>
     __device__ __forceinline__ void reduce(Acc &a, R r) const { a.c = r.sum(a.c); }

@@ -29,6 +29,8 @@ PL_BLOCK = 256               # csrc/grx_peel.h (grx_core_numbers, grx_truss_numb
 PL_SWEEP_MAX_WG = 2048       # and workgroups of the two sweeps over all items (256 nodes resp. arcs each)
 TR_PEEL_MAX_WG = 2048        # csrc/grx_truss.hip: workgroups of the peel (256 / lanes frontier edges each)
 GL_K4_MAX_WG = 8192          # csrc/grx_graphlets.hip: workgroups of the 4-clique kernel (256 / lanes arcs each)
+TD_TYPES = 16                # csrc/grx_triads.hip: the columns of the census,
+TD_MAX_WG = 2048             # workgroups of its pair count and (per column) of its totals (256 items each)
 SQ_WAVE_MAX_WG = 8192        # csrc/grx_square_clustering.hip: workgroups of the wave tier (64 rows each),
 SQ_LDS_MAX_WG = 1024         # of the LDS tier (256 rows each)
 SQ_DENSE_WG = 128            # and of the dense tier (1024 rows each)
@@ -1626,6 +1628,27 @@ def graphlet_orbits(csr: DeviceCSR, want_noninduced: bool = False, want_arc_tria
     _lib.call('grx_graphlet_orbits', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(o.row_ptr), _ptr(o.col), hub_ptr, n_hubs,
               lanes_per_row, _ptr(squares), _ptr(orbits), _ptr(non), _ptr(tri), _ptr(ws), ws_bytes, _stream())
     return orbits, non, tri
+
+
+def triad_census(csr: DeviceCSR, codes: torch.Tensor, want_totals: bool = True, want_arc_triads: bool = False,
+                 lanes: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """grx_triad_census on the structurally symmetric all-neighbours CSR of a directed graph (no diagonal entry; csr.w
+    is not read) and codes uint8[nnz], the direction code of every arc slot (u, v): 1 = only u -> v, 2 = only v -> u,
+    3 = both.  (census int64[16, n] = the triads of each type that contain the node, one contiguous row per type in
+    networkx's order, totals int64[16] = the census of the graph, arc_triads int32[nnz] = the common neighbours of the
+    pair at both of its slots), the last two None unless asked for.  lanes = lanes per row and per arc (4, 8, 16 or
+    32; None = csr.lanes_per_row), with the hub list of that width."""
+    n = csr.n
+    if codes.dtype != torch.uint8 or codes.numel() < csr.nnz or not codes.is_contiguous():
+        raise ValueError('triad_census: codes must be a contiguous uint8 tensor of at least nnz entries')
+    ws, ws_bytes = _workspace('grx_triad_census_workspace_bytes', n, csr.nnz)
+    census = torch.empty((TD_TYPES, n), dtype=torch.int64, device=device())
+    totals = torch.empty(TD_TYPES, dtype=torch.int64, device=device()) if want_totals else None
+    arc = torch.empty(max(csr.nnz, 1), dtype=torch.int32, device=device()) if want_arc_triads else None
+    hub_ptr, n_hubs, lanes_per_row, _keep = _hubs_for(csr, lanes)
+    _lib.call('grx_triad_census', n, _ptr(csr.row_ptr), _ptr(csr.col), _ptr(codes), hub_ptr, n_hubs, lanes_per_row,
+              _ptr(census), _ptr(totals), _ptr(arc), _ptr(ws), ws_bytes, _stream())
+    return census, totals, arc
 
 
 NS_LONG_ROW = 1024       # csrc/grx_neighbor_sense.hip: a row with more arcs than this is walked by a whole workgroup

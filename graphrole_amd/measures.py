@@ -41,7 +41,11 @@ csrc/grx_graphlets.hip: non-induced counts from degrees, triangles per edge, the
 kernel and a 4-clique listing on the degree-oriented graph, then an integer back-substitution, and -- with
 ``edge_betweenness_centrality`` -- the betweenness of every edge, by hops or by weight, as networkx's
 ``edge_betweenness_centrality(G, k, normalized, weight, seed)`` defines it, by the two betweenness files with sigma kept
-and one pass per batch over the arcs of the shortest-path DAGs (csrc/grx_edge_sum.h states the order of its sums).
+and one pass per batch over the arcs of the shortest-path DAGs (csrc/grx_edge_sum.h states the order of its sums), and
+-- with ``triadic_census`` / ``node_triad_census`` -- the triad census of a directed graph (Holland and Leinhardt's 16
+classes of three nodes with their arcs), for the graph as networkx's ``triadic_census(G, nodelist)`` and per node, by
+csrc/grx_triads.hip: the closed triads by one row intersection per adjacent pair of the all-neighbours CSR with one
+direction byte per arc slot, the open and the dyadic ones from neighbour classes, degrees and common neighbours.
 """
 from __future__ import annotations
 
@@ -1719,6 +1723,188 @@ def graphlet_counts(G) -> pd.Series:
     totals = graphlet_degree_vectors(G).attrs['graphlets']
     return pd.Series([totals[name] for name in _GRAPHLETS], index=pd.Index(list(_GRAPHLETS)), dtype=np.int64,
                      name='graphlet_counts')
+
+
+# ------------------------------------------------------------------------------------------------- triad census
+#: networkx's TRIAD_NAMES, in its order: the 16 isomorphism classes of three nodes with their arcs
+TRIAD_NAMES = ('003', '012', '102', '021D', '021U', '021C', '111D', '111U', '030T', '030C', '201', '120D', '120U',
+               '120C', '210', '300')
+_TRIAD_COLUMNS = [f'triad_{name}' for name in TRIAD_NAMES]
+
+
+def _triad_refusals(graph, what: str) -> None:
+    """The triad census is defined on a simple directed graph: an undirected graph, a multigraph (by the adapter's flag
+    or by parallel arcs in its edge list) and a self-loop are refused, each with its remedy.  Read from the adapter and
+    the host CSR: no device work."""
+    if not graph.directed:
+        raise NotImplementedError(f'{what}: networkx does not implement nx.triadic_census(G) for an undirected graph; '
+                                  f'pass G.to_directed(), as its docstring advises (only 003, 102, 201 and 300 occur '
+                                  f'then)')
+    if _has_parallel_edges(graph):
+        raise NotImplementedError(f'{what}: a triad is classified by the arcs present, not by how many; a multigraph '
+                                  f'or a graph with parallel arcs is not computed here: pass nx.DiGraph(G), which '
+                                  f'merges them')
+    if getattr(graph.to_csr(), 'n_loops', 1) > 0:
+        raise NotImplementedError(f'{what}: a graph with a self-loop is not computed here (networkx\'s own nodelist '
+                                  f'path miscounts there, so there is no authority); remove them first: '
+                                  f'G.remove_edges_from(nx.selfloop_edges(G))')
+
+
+def _code_csr(n: int, a: np.ndarray, b: np.ndarray):
+    """(row_ptr int64, col int32, codes uint8) of the distinct arcs a -> b (no self-loops) on the rows 0 .. n - 1: the
+    structurally symmetric all-neighbours CSR and the direction code of every slot (u, v): 1 = only u -> v, 2 = only
+    v -> u, 3 = both."""
+    key, inverse = np.unique(np.concatenate([a, b]) * np.int64(max(n, 1)) + np.concatenate([b, a]), return_inverse=True)
+    inverse = inverse.ravel()
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=row_ptr[1:])
+    codes = np.zeros(len(key), dtype=np.uint8)
+    codes[inverse[:len(a)]] |= 1                                # the arc at its tail's slot
+    codes[inverse[len(a):]] |= 2                                # and seen from its head
+    return row_ptr, (key % max(n, 1)).astype(np.int32), codes
+
+
+def _triad_csr(graph, K):
+    """(device CSR, codes uint8 device tensor, (row_ptr, col, codes) on the host) of grx_triad_census: the structurally
+    symmetric CSR of networkx's all_neighbors in internal row order (no diagonal entry: self-loops are refused before)
+    and the direction code of every slot.  Cached on the adapter."""
+    cached = graph.__dict__.get('_triad')
+    if cached is None:
+        row_ptr, col, inverse, vals = _symmetric_union(graph, False)
+        codes = np.zeros(len(col), dtype=np.uint8)
+        codes[inverse[:len(vals)]] |= 1                         # arc (u, v) as given
+        codes[inverse[len(vals):]] |= 2                         # and seen from its head
+        csr = K.DeviceCSR(row_ptr, col)
+        cached = graph.__dict__['_triad'] = (csr, K.to_device(codes if len(codes) else np.zeros(1, dtype=np.uint8)),
+                                             (row_ptr, col, codes))
+    return cached
+
+
+def _triad_totals(K, csr, codes) -> List[int]:
+    """The census of the graph from one call: the 16 totals, 128 bytes read back."""
+    return [int(x) for x in np.asarray(K.to_host(K.triad_census(csr, codes, want_totals=True)[1]))[:16]]
+
+
+def _edgeless_census(n: int) -> List[int]:
+    return [n * (n - 1) * (n - 2) // 6] + [0] * 15
+
+
+def _triadic_census(graph, removed: Optional[np.ndarray] = None) -> List[int]:
+    """The census of the graph, or of what is left of it without the rows `removed` of the sorted labels (the induced
+    subgraph, built on the host from the arcs)."""
+    g = graph.to_csr()
+    if g.n == 0 or g.num_edges == 0:
+        return _edgeless_census(g.n - (0 if removed is None else len(removed)))
+    K = graph._K()
+    csr, codes, (row_ptr, col, host_codes) = _triad_csr(graph, K)
+    if removed is None:
+        return _triad_totals(K, csr, codes)
+    keep = np.ones(g.n, dtype=bool)
+    keep[np.asarray(graph._device_graph()[0].inv, dtype=np.int64)[removed]] = False
+    new_row = np.cumsum(keep) - 1
+    rows = np.repeat(np.arange(g.n, dtype=np.int64), np.diff(row_ptr))
+    arc = (host_codes & 1).astype(bool) & keep[rows] & keep[col]
+    left = int(keep.sum())
+    if not arc.any():
+        return _edgeless_census(left)
+    sub_ptr, sub_col, sub_codes = _code_csr(left, new_row[rows[arc]], new_row[col[arc].astype(np.int64)])
+    return _triad_totals(K, K.DeviceCSR(sub_ptr, sub_col), K.to_device(sub_codes))
+
+
+def triadic_census(G, nodelist=None) -> dict:
+    """
+    The triad census of a directed graph on the GPU -- how many of the 16 isomorphism classes of three nodes with
+    their arcs (Holland and Leinhardt 1970) occur: ``nx.triadic_census(G, nodelist)`` of networkx 3.4.2 (triads.py).
+    The names say Mutual, Asymmetric and Null pairs, then Down, Up, Cyclic or Transitive: ``003`` (no arc), ``012``,
+    ``102``, ``021D``, ``021U``, ``021C``, ``111D``, ``111U``, ``030T``, ``030C``, ``201``, ``120D``, ``120U``,
+    ``120C``, ``210``, ``300`` (the mutual clique).  One call of grx_triad_census (csrc/grx_triads.hip); only the
+    totals, 128 bytes, come back.
+
+    :param G: any directed graph ``node_measures`` accepts, without parallel arcs and self-loops
+    :param nodelist: None = every triad; otherwise a list of distinct nodes: only the triads with at least one member
+      in it count.  Computed as the census of G minus the census of G without the listed nodes (a triad with no listed
+      member is a triad of that induced subgraph): two device calls
+    :return: dict name -> Python int, the 16 names in networkx's order; equal to networkx
+    :raises NotImplementedError: G is undirected (pass ``G.to_directed()``), a multigraph or has parallel arcs (pass
+      ``nx.DiGraph(G)``) or has a self-loop (``G.remove_edges_from(nx.selfloop_edges(G))``)
+    :raises ValueError: `nodelist` holds a node twice or something that is not a node, as networkx
+
+    Exact (integers) while C(n - 1, 2) is below 2^53.  ``node_triad_census`` is the per-node table.
+    """
+    graph = _adapter(G)
+    _triad_refusals(graph, 'triadic_census')
+    removed = None
+    if nodelist is not None:
+        nodelist = list(nodelist)
+        members = set(graph.get_nodes())
+        try:
+            listed = {v for v in nodelist if v in members}
+        except TypeError:                                      # unhashable: not a node
+            listed = set()
+        if len(listed) != len(nodelist):
+            raise ValueError('nodelist includes duplicate nodes or nodes not in G')
+        if not nodelist:                                       # no triad has a member in an empty list
+            return dict.fromkeys(TRIAD_NAMES, 0)
+        removed = _rows_of(graph, nodelist)
+    whole = _triadic_census(graph)
+    if removed is not None:
+        whole = [a - b for a, b in zip(whole, _triadic_census(graph, removed))]
+    return dict(zip(TRIAD_NAMES, whole))
+
+
+def node_triad_census(G, nodes=None):
+    """
+    The triad census of every node of a directed graph on the GPU: for each of the 16 triad types, the number of
+    triads of that type that contain the node -- ``nx.triadic_census(G, nodelist=[v])`` for every v at once, the
+    directed counterpart of orbits 0-3 of ``graphlet_degree_vectors`` and the classical signature of a node's role in
+    a directed network.  It separates a broadcaster (many ``021D`` around it) from a sink (``021U``), a relay
+    (``021C``), a member of a feed-forward hierarchy (``030T``), of a cycle (``030C``) and of a mutual clique
+    (``300``), which Fagiolo's ``clustering(D)`` folds into one number.
+
+    One call of grx_triad_census (csrc/grx_triads.hip): only the closed triads are enumerated, by one row intersection
+    per adjacent pair; the open ones follow from the classes of every node's neighbours (out-only, in-only, mutual) by
+    a fixed 7 x 6 integer matrix, the dyadic ones from degrees and common neighbours, ``003`` from the rest.
+
+    :param G: any directed graph ``node_measures`` accepts, without parallel arcs and self-loops
+    :param nodes: None = every node; a node = that node only; otherwise the members of the iterable, each of which
+      must be a node
+    :return: DataFrame of int64 columns ``triad_003`` ... ``triad_300`` indexed by the sorted node labels (the index of
+      ``node_measures``, so ``M = M.join(node_triad_census(D))`` adds the columns to a table for ``sense_making``) or
+      by the sorted members of `nodes`; a Series (index = the column names) for a single node.  ``.attrs['census']`` =
+      the census of the WHOLE graph (``triadic_census(G)``) as a dict: every column sums to three times its entry
+    :raises NotImplementedError: as ``triadic_census``
+    :raises KeyError: a member of `nodes` is not a node
+
+    Exact (integers; equal to networkx and to enumeration of all 3-subsets) while C(n - 1, 2) is below 2^53; the same
+    bits in every run and for every relabelling.  No column is in ``CATALOGUE``: this function is the way in.
+    """
+    graph = _adapter(G)
+    _triad_refusals(graph, 'node_triad_census')
+    single, rows = False, None
+    if nodes is not None:
+        try:
+            single = nodes in set(graph.get_nodes())
+        except TypeError:                                      # unhashable: a container of nodes
+            pass
+        rows = _member_rows(graph, [nodes] if single else nodes)
+    g = graph.to_csr()
+    if g.n == 0 or g.num_edges == 0:
+        index = _label_index(graph) if g.n else pd.Index([])
+        frame = pd.DataFrame(np.zeros((g.n, 16), dtype=np.int64), index=index, columns=_TRIAD_COLUMNS)
+        frame['triad_003'] = (g.n - 1) * (g.n - 2) // 2
+        census = _edgeless_census(g.n)
+    else:
+        K = graph._K()
+        csr, codes, _ = _triad_csr(graph, K)
+        columns, totals, _ = K.triad_census(csr, codes, want_totals=True)
+        frame = graph._frame(_TRIAD_COLUMNS, [columns[k] for k in range(16)], [np.dtype('int64')] * 16)
+        census = [int(x) for x in np.asarray(K.to_host(totals))[:16]]
+    if rows is not None:
+        frame = frame.iloc[rows]
+        if single:
+            frame = frame.iloc[0]
+    frame.attrs['census'] = dict(zip(TRIAD_NAMES, census))
+    return frame
 
 
 # ----------------------------------------------------------------------------------------------- NeighborSense

@@ -40,7 +40,8 @@ extern "C" {
                                     grx_neighbor_roles (the neighbour-role table of NeighborSense) and
                                     grx_similar_rows (structural similarity: exact top-k nearest rows) and
                                     grx_components / grx_reachable (connected, weak and strong components, closures) and
-                                    grx_edge_betweenness / grx_weighted_edge_betweenness (edge betweenness centrality)
+                                    grx_edge_betweenness / grx_weighted_edge_betweenness (edge betweenness centrality) and
+                                    grx_triad_census (the triad census of a directed graph, per node and per graph)
                                     0.10.0: grx_biconnected (biconnected-component counts / articulation points of the
                                     sense-making measures)
                                     0.9.0: grx_distance_sums (closeness and harmonic centrality of the sense-making
@@ -1321,6 +1322,37 @@ int grx_graphlet_orbits(int64_t n, const int64_t *d_row_ptr, const int32_t *d_co
                         const int32_t *d_o_col, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,
                         const int64_t *d_squares, int64_t *d_orbits, int64_t *d_noninduced, int32_t *d_arc_triangles,
                         void *d_workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * grx_triad_census: the triad census of a directed graph per node (Holland and Leinhardt 1970; networkx's
+ *   triadic_census): for each of the 16 isomorphism classes of three nodes with their arcs, the number of triads of
+ *   that class that contain the node.  Columns in networkx's order:
+ *     0 003 | 1 012 | 2 102 | 3 021D | 4 021U | 5 021C | 6 111D | 7 111U | 8 030T | 9 030C | 10 201 | 11 120D |
+ *     12 120U | 13 120C | 14 210 | 15 300
+ *   d_row_ptr / d_col: the STRUCTURALLY SYMMETRIC CSR of all neighbours (predecessors and successors): columns
+ *   ascending and distinct inside a row, no diagonal entry; n < 2^31.  Rows longer than GRX_HUB_FACTOR * lanes_per_row
+ *   (4, 8, 16 or 32) must be listed in d_hub_rows (the row passes' launch shape; the intersections have no hub path).
+ *   d_codes: uint8[nnz], the direction code of arc slot (u, v): 1 = only u -> v, 2 = only v -> u, 3 = both; the code at
+ *   (v, u) is the mirror of the one at (u, v).  Only the two low bits are read.
+ *   d_census: int64[16][n], overwritten, one contiguous column per type.  d_totals: int64[16] or NULL, the census of
+ *   the graph: the column sums divided by 3, summed on the device in integers.  d_arc_triads: int32[nnz] or NULL, the
+ *   common neighbours of the pair (the closed triads through it) at BOTH slots of the pair.
+ *   Method: see the header of csrc/grx_triads.hip: only the closed triads are enumerated, the open ones follow from
+ *   the neighbour classes by a fixed 7 x 6 integer matrix and the dyadic ones from degrees and common neighbours.
+ *   Cost: one row intersection per adjacent pair (min(d_u, d_v) * ceil(log2 max(d_u, d_v)) dependent 4-byte gathers),
+ *   two one-byte gathers and six 64-bit integer atomics per closed triad, two row passes.
+ *   Exact: integer atomics only and no result depends on their order, so every output has the same bits in every run,
+ *   for every lanes_per_row and for every relabelling of the rows.  The row sums are carried in doubles that hold
+ *   integers: the outputs are exact while every intermediate (C(n - 1, 2); a sum of degrees over a row) is below 2^53;
+ *   the final arithmetic is int64.
+ *   d_workspace: grx_triad_census_workspace_bytes(n, nnz) bytes (40 n + 8 nnz: five 8-byte vectors per node and two
+ *   int32 per arc, each array rounded up to 256 bytes).  n == 0: GRX_OK with nothing launched; nnz == 0: column 003 is
+ *   C(n - 1, 2).  Otherwise the call reads row_ptr[n] back and so waits for the stream once, before its first launch.
+ */
+size_t grx_triad_census_workspace_bytes(int64_t n, int64_t nnz);
+int grx_triad_census(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const uint8_t *d_codes,
+                     const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row, int64_t *d_census,
+                     int64_t *d_totals, int32_t *d_arc_triads, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /*
  * grx_neighbor_roles: the neighbour-role table of RolX NeighborSense (Henderson et al., KDD 2012, section 4), the
