@@ -14,9 +14,11 @@
 //   chunk are skipped.  The levels run as a device-steered round loop (grx_common.h); the level word ends as the depth.
 // Backward, level l = depth .. 1: pull over the OUT-adjacency.  delta(v) = sum over successors w at level l + 1 of
 //   sigma(v) * coeff(w), each term networkx's own product; then coeff(v) = (1 + delta(v)) / sigma(v) replaces sigma(v).
-// Accumulation: bc[v] adds the sources' contributions one after another in the caller's order (the sources of a
-//   batch in lane order, batches in order), so the result has the same bits for every B.  A final kernel
+// Accumulation (grx_brandes.h): bc[v] adds the sources' contributions one after another in the caller's order (the
+//   sources of a batch in lane order, batches in order), so the result has the same bits for every B.  A final kernel
 //   multiplies by the scale of _rescale.  No floating-point atomics (the per-lane reach counts are integer adds).
+// The argument checks, the per-batch sequence of these passes and the finish are br_open and br_run of grx_brandes.h,
+// shared with grx_weighted_betweenness.hip; BwSide below is what this file hands them.
 //
 // grx_edge_betweenness (networkx's edge_betweenness_centrality, _accumulate_edges, _rescale_e) runs the same forward and
 // backward kernels with coeff written to an array of its own (the backward kernels are templated on that), so that
@@ -32,64 +34,50 @@
 // IEEE operation, as in networkx.
 #pragma clang fp contract(off)
 
-#include "grx_common.h"
-#include "grx_edge_sum.h"
-
-#include <algorithm>
+#include "grx_brandes.h"
 
 namespace {
 
 constexpr int BW_BLOCK = 256;
 constexpr int BW_WAVES = BW_BLOCK / GRX_WAVE;
+static_assert(BW_WAVES == BR_PARTS, "a hub workgroup's wavefronts are the parts br_combine4 adds");
 constexpr int BW_MAX_BATCH = 256;
-constexpr int BW_LEVEL_BATCH = 8;                            // forward levels enqueued between two read-backs
 constexpr int BW_MAX_ROW_BLOCKS = 1024;
 constexpr int BW_MAX_BLOCKS = 2048;                           // grid of the per-element launches
 constexpr size_t BW_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of B
 
 constexpr int32_t BW_IDLE = 0x7fffffff;
 
+// The workspace, laid out once: level (int32), sigma and delta (fp64) per (node, source) -- 20 bytes a cell; coeff
+// (fp64) in an array of its own for grx_edge_betweenness only, 28 bytes a cell (otherwise coeff replaces sigma); the
+// per-lane reach counts and the control words
+struct BwWs {
+    BrLayout lay;
+    int32_t *level;
+    double *sigma, *delta, *coeff;
+    int32_t *reach, *ctrl;
+    BwWs(void *base, int64_t n, int B, bool keep_sigma) : lay(base, n, B)
+    {
+        level = lay.per_cell<int32_t>();
+        sigma = lay.per_cell<double>();
+        delta = lay.per_cell<double>();
+        coeff = keep_sigma ? lay.per_cell<double>() : nullptr;
+        reach = lay.take<int32_t>(B);
+        ctrl = lay.take<int32_t>(GRX_CTRL_MAX_WORDS);
+    }
+    size_t bytes() const { return lay.used; }
+};
+
 // B of batch = 0: the widest multiple of 64 up to 256 whose state fits BW_DEFAULT_STATE_BYTES (at least 64, so above
 // ~3.35 M nodes the state is 20 n 64 bytes, more than the budget), and no wider than the source list
-// (grx_edge_betweenness: 28 bytes per cell, coeff has an array of its own)
-int choose_batch(int64_t n, int batch, int64_t n_sources, bool keep_sigma = false)
+int choose_batch(int64_t n, int batch, int64_t n_sources, bool keep_sigma)
 {
     if (batch > 0) return batch;
-    // level 4 + sigma 8 + delta 8 (+ coeff 8) bytes per (node, source)
-    const size_t per_lane = (size_t)(n > 0 ? n : 1) * (keep_sigma ? 28 : 20);
+    const size_t per_lane = (size_t)(n > 0 ? n : 1) * BwWs(nullptr, n, GRX_WAVE, keep_sigma).lay.cell_bytes;
     const int64_t b = (int64_t)(BW_DEFAULT_STATE_BYTES / per_lane) / GRX_WAVE * GRX_WAVE;
     const int64_t widest = std::max<int64_t>(GRX_WAVE, std::min<int64_t>(b, BW_MAX_BATCH));
     const int64_t needed = std::max<int64_t>(GRX_WAVE, grx_ceil_div(n_sources, GRX_WAVE) * GRX_WAVE);
     return (int)std::min<int64_t>(widest, needed);
-}
-
-size_t ws_bytes(int64_t n, int B, bool keep_sigma = false)
-{
-    const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)B;
-    return grx_align_up(cells * 4, 256) + (keep_sigma ? 3 : 2) * grx_align_up(cells * 8, 256) +
-           grx_align_up((size_t)B * 4, 256) + 256;
-}
-
-struct BwWs {
-    int32_t *level;
-    double *sigma, *delta;
-    double *coeff;                                           // grx_edge_betweenness only; otherwise coeff replaces sigma
-    int32_t *reach, *ctrl;
-};
-
-BwWs carve(void *base, int64_t n, int B, bool keep_sigma = false)
-{
-    const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)B;
-    char *p = reinterpret_cast<char *>(base);
-    BwWs w;
-    w.level = reinterpret_cast<int32_t *>(p); p += grx_align_up(cells * 4, 256);
-    w.sigma = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
-    w.delta = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
-    w.coeff = nullptr;
-    if (keep_sigma) { w.coeff = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256); }
-    w.reach = reinterpret_cast<int32_t *>(p); p += grx_align_up((size_t)B * 4, 256);
-    w.ctrl = reinterpret_cast<int32_t *>(p);
-    return w;
 }
 
 // -1 (not reached) in the lanes of the batch's sources, BW_IDLE in the unused lanes of a last, partial batch (settled
@@ -229,7 +217,7 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_forward_hub_kernel(const int64_t 
     part[wave][lane] = pull_sigma(b + wave, e, BW_WAVES, col, level, sigma, B, off, l);
     __syncthreads();
     if (wave != 0) return;
-    const double acc = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+    const double acc = br_combine4(part, lane);
     const bool hit = open && acc != 0.0;
     if (hit) {
         level[cell] = l + 1;
@@ -237,14 +225,6 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_forward_hub_kernel(const int64_t 
         atomicAdd(&reach[off], 1);
     }
     if (__ballot(hit) && lane == 0) ctrl[GRX_CT_FOUND] = 1;
-}
-
-// networkx _accumulate_*: coeff = (1 + delta[w]) / sigma[w]; delta[v] += sigma[v] * coeff
-__device__ __forceinline__ void settle(int64_t cell, double d, double sv, double *__restrict__ coeff,
-                                       double *__restrict__ delta)
-{
-    delta[cell] = d;
-    coeff[cell] = (1.0 + d) / sv;                            // coeff(v) for the level above
 }
 
 // backward, level l: cells at level l pull delta from their successors at l + 1; one wavefront per (row, chunk).
@@ -269,7 +249,7 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_backward_kernel(int64_t n, const 
         if (e - b > hub_degree) continue;                   // bw_backward_hub_kernel
         const double sv = mine ? sigma[cell] : 1.0;
         const double d = pull_delta(b, e, 1, col, level, coeff, B, off, l + 1, sv);
-        if (mine) settle(cell, d, sv, coeff, delta);
+        if (mine) br_settle(cell, d, sv, coeff, delta);
     }
 }
 
@@ -295,36 +275,8 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_backward_hub_kernel(const int64_t
     part[wave][lane] = pull_delta(b + wave, e, BW_WAVES, col, level, coeff, B, off, l + 1, sv);
     __syncthreads();
     if (wave != 0 || !mine) return;
-    settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, coeff, delta);
+    br_settle(cell, br_combine4(part, lane), sv, coeff, delta);
 }
-
-// bc[v] += the contributions of the batch's sources in lane order (networkx: betweenness[w] += delta[w] for w != s;
-// with endpoints betweenness[s] += len(S) - 1 and betweenness[w] += delta[w] + 1)
-__global__ __launch_bounds__(BW_BLOCK) void bw_accumulate_kernel(int64_t n, int B, int count, int endpoints,
-                                                                 const int32_t *__restrict__ level,
-                                                                 const double *__restrict__ delta,
-                                                                 const int32_t *__restrict__ reach,
-                                                                 double *__restrict__ bc)
-{
-    for (int64_t v = (int64_t)blockIdx.x * BW_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BW_BLOCK) {
-        const int32_t *lv = level + v * B;
-        const double *dv = delta + v * B;
-        double acc = bc[v];
-        for (int b = 0; b < count; ++b) {
-            const int l = lv[b];
-            if (l > 0 && l != BW_IDLE) acc += endpoints ? dv[b] + 1.0 : dv[b];
-            else if (l == 0 && endpoints) acc += (double)(reach[b] - 1);
-        }
-        bc[v] = acc;
-    }
-}
-
-__global__ __launch_bounds__(BW_BLOCK) void bw_scale_kernel(int64_t n, double scale, double *__restrict__ bc)
-{
-    for (int64_t v = (int64_t)blockIdx.x * BW_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * BW_BLOCK)
-        bc[v] *= scale;
-}
-
 
 // grx_edge_betweenness, after the backward loop of a batch: the arcs [b, e) with stride `step` of row v, the wavefront's
 // lanes being the sources of one 64-lane chunk after another.  Lane `off` holds sigma(v) * coeff(w) when v -> w is an
@@ -381,92 +333,77 @@ __global__ __launch_bounds__(BW_BLOCK) void bw_edge_hub_kernel(const int64_t *__
     edge_row(v, row_ptr[v] + wave, row_ptr[v + 1], BW_WAVES, col, level, sigma, coeff, B, lane, ebc);
 }
 
-// Both entry points: EDGES = false is grx_betweenness (d_out = bc, one value per node), true is grx_edge_betweenness
-// (d_out = ebc, one value per arc of the out CSR; `endpoints` is not read)
+// What br_run drives: the carved state of one call.  EDGES = false is grx_betweenness, true is grx_edge_betweenness
 template <bool EDGES>
-int run(const char *name, int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
-        int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
-        const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, const int32_t *d_sources,
-        int64_t n_sources, int endpoints, double scale, int batch, double *d_out, void *d_workspace,
-        size_t workspace_bytes, void *stream)
+struct BwSide {
+    int64_t n;
+    SpPull out, in;                                          // backward and the edge pass pull over `out`, forward over `in`
+    bool directed;
+    int B;
+    BwWs ws;
+    hipStream_t st;
+
+    unsigned chunks() const { return (unsigned)(B / GRX_WAVE); }
+    unsigned row_blocks() const { return grx_grid(n, BW_WAVES, BW_MAX_ROW_BLOCKS); }
+    static const char *forward_refusal()
+    {
+        return EDGES ? "grx_edge_betweenness: the forward pass did not end after %lld levels"
+                     : "grx_betweenness: the forward pass did not end after %lld levels";
+    }
+    int begin(const int32_t *d_src, int count) const
+    {
+        const int64_t cells = n * (int64_t)B;
+        bw_level_init_kernel<<<grx_grid(cells, BW_BLOCK, BW_MAX_BLOCKS), BW_BLOCK, 0, st>>>(cells, B, count, ws.level);
+        bw_source_init_kernel<<<1, BW_MAX_BATCH, 0, st>>>(n, B, count, d_src, ws.level, ws.sigma, ws.reach, ws.ctrl);
+        return GRX_OK;
+    }
+    int forward_round() const
+    {
+        if (in.n_hub_rows)
+            bw_forward_hub_kernel<<<dim3((unsigned)in.n_hub_rows, chunks()), BW_BLOCK, 0, st>>>(
+                in.row_ptr, in.col, in.hub_rows, B, ws.level, ws.sigma, ws.reach, ws.ctrl);
+        bw_forward_kernel<<<dim3(row_blocks(), chunks()), BW_BLOCK, 0, st>>>(n, in.row_ptr, in.col, in.hub_degree, B,
+                                                                             ws.level, ws.sigma, ws.reach, ws.ctrl);
+        return grx_frontier_advance(ws.ctrl, st);
+    }
+    void after_forward(int) const {}                         // the forward kernels counted reach
+    void backward(int l) const
+    {
+        if (out.n_hub_rows)
+            bw_backward_hub_kernel<EDGES><<<dim3((unsigned)out.n_hub_rows, chunks()), BW_BLOCK, 0, st>>>(
+                out.row_ptr, out.col, out.hub_rows, B, l, ws.level, ws.sigma, ws.coeff, ws.delta);
+        bw_backward_kernel<EDGES><<<dim3(row_blocks(), chunks()), BW_BLOCK, 0, st>>>(
+            n, out.row_ptr, out.col, out.hub_degree, B, l, ws.level, ws.sigma, ws.coeff, ws.delta);
+    }
+    void edge_pass(double *d_ebc) const
+    {
+        if (out.n_hub_rows)
+            bw_edge_hub_kernel<<<(unsigned)out.n_hub_rows, BW_BLOCK, 0, st>>>(out.row_ptr, out.col, out.hub_rows, B,
+                                                                              ws.level, ws.sigma, ws.coeff, d_ebc);
+        bw_edge_kernel<<<row_blocks(), BW_BLOCK, 0, st>>>(n, out.row_ptr, out.col, out.hub_degree, B, ws.level,
+                                                          ws.sigma, ws.coeff, d_ebc);
+    }
+    const int32_t *level() const { return ws.level; }
+    int stride() const { return B; }
+};
+
+// the argument checks and the batches of both entry points (d_out = bc resp. ebc; `endpoints` is 0 for the edges)
+template <bool EDGES>
+int entry(const char *name, int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
+          int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
+          const int32_t *d_in_hub_rows, int64_t n_in_hub_rows, int in_lanes_per_row, const int32_t *d_sources,
+          int64_t n_sources, int endpoints, double scale, int batch, double *d_out, void *d_workspace,
+          size_t workspace_bytes, void *stream)
 {
-    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "%s: n = %lld out of range", name, (long long)n);
-    GRX_REQUIRE(d_row_ptr && d_col && d_out && d_workspace, "%s: null pointer", name);
-    GRX_REQUIRE(n_sources >= 0 && (n_sources == 0 || d_sources), "%s: source list", name);
     GRX_REQUIRE(batch == 0 || (batch > 0 && batch <= BW_MAX_BATCH && batch % GRX_WAVE == 0),
                 "%s: batch must be 0 or a multiple of 64 up to %d (got %d)", name, BW_MAX_BATCH, batch);
-    const bool directed = d_in_row_ptr != nullptr;
-    GRX_REQUIRE(!directed || d_in_col, "%s: d_in_col is required with d_in_row_ptr", name);
-    if (!directed) {                                         // undirected: the CSR is its own in-adjacency
-        d_in_col = d_col;
-        d_in_hub_rows = d_hub_rows;
-        n_in_hub_rows = n_hub_rows;
-        in_lanes_per_row = lanes_per_row;
-    }
-    GRX_REQUIRE(lanes_per_row >= 1 && in_lanes_per_row >= 1, "%s: lanes_per_row must be >= 1", name);
-    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows) && n_in_hub_rows >= 0 &&
-                    (n_in_hub_rows == 0 || d_in_hub_rows), "%s: hub list", name);
     const int B = choose_batch(n, batch, n_sources, EDGES);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, B, EDGES), "%s: workspace %zu bytes, need %zu", name, workspace_bytes,
-                ws_bytes(n, B, EDGES));
-    hipStream_t st = grx_stream(stream);
-    const BwWs ws = carve(d_workspace, n, B, EDGES);
-    const int chunks = B / GRX_WAVE;
-    const unsigned egrid = grx_grid(n, BW_BLOCK, BW_MAX_BLOCKS);
-    const unsigned row_blocks = grx_grid(n, BW_WAVES, BW_MAX_ROW_BLOCKS);
-    const dim3 row_grid(row_blocks, (unsigned)chunks);
-    const int64_t out_hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
-    const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
-    const int64_t cells = n * (int64_t)B;
-    const int64_t *in_rp = directed ? d_in_row_ptr : d_row_ptr;
-
-    if (EDGES) eb_rows<EB_ZERO>(n, d_row_ptr, d_col, 0.0, d_out, st);
-    else grx_fill64(reinterpret_cast<uint64_t *>(d_out), n, 0, st);
-    GRX_LAUNCH_CHECK();
-    for (int64_t first = 0; first < n_sources; first += B) {
-        const int count = (int)std::min<int64_t>(B, n_sources - first);
-        bw_level_init_kernel<<<grx_grid(cells, BW_BLOCK, BW_MAX_BLOCKS), BW_BLOCK, 0, st>>>(cells, B, count, ws.level);
-        bw_source_init_kernel<<<1, BW_MAX_BATCH, 0, st>>>(n, B, count, d_sources + first, ws.level, ws.sigma, ws.reach,
-                                                          ws.ctrl);
-        GRX_LAUNCH_CHECK();
-        int32_t h[2];
-        // a BFS has at most n levels; one more launch finds the empty frontier
-        const int rc = grx_run_rounds(
-            EDGES ? "grx_edge_betweenness: the forward pass did not end after %lld levels"
-                  : "grx_betweenness: the forward pass did not end after %lld levels",
-            BW_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
-                if (n_in_hub_rows)
-                    bw_forward_hub_kernel<<<dim3((unsigned)n_in_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
-                        in_rp, d_in_col, d_in_hub_rows, B, ws.level, ws.sigma, ws.reach, ws.ctrl);
-                bw_forward_kernel<<<row_grid, BW_BLOCK, 0, st>>>(n, in_rp, d_in_col, in_hub_degree, B, ws.level,
-                                                                 ws.sigma, ws.reach, ws.ctrl);
-                return grx_frontier_advance(ws.ctrl, st);
-            });
-        if (rc != GRX_OK) return rc;
-        for (int l = h[GRX_CT_LEVEL]; l >= 1; --l) {        // deepest level first; the sources need no delta
-            if (n_hub_rows)
-                bw_backward_hub_kernel<EDGES><<<dim3((unsigned)n_hub_rows, (unsigned)chunks), BW_BLOCK, 0, st>>>(
-                    d_row_ptr, d_col, d_hub_rows, B, l, ws.level, ws.sigma, ws.coeff, ws.delta);
-            bw_backward_kernel<EDGES><<<row_grid, BW_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, l,
-                                                                     ws.level, ws.sigma, ws.coeff, ws.delta);
-            GRX_LAUNCH_CHECK();
-        }
-        if (EDGES) {
-            if (n_hub_rows)
-                bw_edge_hub_kernel<<<(unsigned)n_hub_rows, BW_BLOCK, 0, st>>>(d_row_ptr, d_col, d_hub_rows, B, ws.level,
-                                                                              ws.sigma, ws.coeff, d_out);
-            bw_edge_kernel<<<row_blocks, BW_BLOCK, 0, st>>>(n, d_row_ptr, d_col, out_hub_degree, B, ws.level, ws.sigma,
-                                                            ws.coeff, d_out);
-        } else {
-            bw_accumulate_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, B, count, endpoints, ws.level, ws.delta, ws.reach,
-                                                             d_out);
-        }
-        GRX_LAUNCH_CHECK();
-    }
-    if (EDGES) eb_finish(n, d_row_ptr, d_col, directed, scale, d_out, st);
-    else bw_scale_kernel<<<egrid, BW_BLOCK, 0, st>>>(n, scale, d_out);
-    GRX_LAUNCH_CHECK();
-    return GRX_OK;
+    BwSide<EDGES> side{n, {}, {}, false, B, BwWs(d_workspace, n, B, EDGES), grx_stream(stream)};
+    const int rc = br_open(name, n, d_row_ptr, d_col, nullptr, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr,
+                           d_in_col, nullptr, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources,
+                           d_out, d_workspace, workspace_bytes, side.ws.bytes(), side.out, side.in, side.directed);
+    if (rc != GRX_OK) return rc;
+    return br_run<EDGES>(side, d_sources, n_sources, endpoints, scale, d_out, side.st);
 }
 
 }  // namespace
@@ -475,7 +412,7 @@ extern "C" {
 
 size_t grx_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources)
 {
-    return ws_bytes(n, choose_batch(n, batch, n_sources));
+    return BwWs(nullptr, n, choose_batch(n, batch, n_sources, false), false).bytes();
 }
 
 int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
@@ -484,14 +421,14 @@ int grx_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
                     const int32_t *d_sources, int64_t n_sources, int endpoints, double scale, int batch, double *d_bc,
                     void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    return run<false>("grx_betweenness", n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr,
-                      d_in_col, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, endpoints, scale,
-                      batch, d_bc, d_workspace, workspace_bytes, stream);
+    return entry<false>("grx_betweenness", n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr,
+                        d_in_col, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, endpoints,
+                        scale, batch, d_bc, d_workspace, workspace_bytes, stream);
 }
 
 size_t grx_edge_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources)
 {
-    return ws_bytes(n, choose_batch(n, batch, n_sources, true), true);
+    return BwWs(nullptr, n, choose_batch(n, batch, n_sources, true), true).bytes();
 }
 
 int grx_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
@@ -500,9 +437,9 @@ int grx_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_c
                          const int32_t *d_sources, int64_t n_sources, double scale, int batch, double *d_ebc,
                          void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    return run<true>("grx_edge_betweenness", n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr,
-                     d_in_col, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, 0, scale, batch,
-                     d_ebc, d_workspace, workspace_bytes, stream);
+    return entry<true>("grx_edge_betweenness", n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, lanes_per_row,
+                       d_in_row_ptr, d_in_col, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, 0,
+                       scale, batch, d_ebc, d_workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -85,6 +85,16 @@ static inline unsigned grx_grid(int64_t items, int64_t per_block, int64_t cap)
 void grx_fill32(int32_t *d_dst, int64_t count, int32_t value, hipStream_t st);
 void grx_fill64(uint64_t *d_dst, int64_t count, uint64_t value, hipStream_t st);
 
+// the CSR a pass pulls over (a relaxation pulls over the in-adjacency to walk the out-arcs from each source)
+struct SpPull {
+    int64_t n;
+    const int64_t *row_ptr;
+    const int32_t *col;
+    const double *w;                                         // NULL: every weight is 1
+    const int32_t *hub_rows;
+    int64_t n_hub_rows, hub_degree;
+};
+
 // ---- round loops the device steers (BFS levels, peeling rounds, power iterations) -------------------------------
 // A loop whose trip count only the device knows keeps a few int32 control words at the end of its workspace.  In every
 // layout word 0 is `done` and word 1 the counter (BFS level, peeling layer, iteration count); the BFS loops share the

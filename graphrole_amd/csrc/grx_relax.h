@@ -15,16 +15,6 @@ constexpr int SP_MAX_ROW_BLOCKS = 8192;
 
 bool sp_valid_batch(int s) { return s == 16 || s == 32 || s == 64; }
 
-// the CSR one relaxation pulls over: the in-adjacency to walk the out-arcs from each source
-struct SpPull {
-    int64_t n;
-    const int64_t *row_ptr;
-    const int32_t *col;
-    const double *w;                                         // NULL: every weight is 1
-    const int32_t *hub_rows;
-    int64_t n_hub_rows, hub_degree;
-};
-
 // min of `best` and fl(dist(u, lane) + w(u -> v)) over the arcs [b, e) with stride `step`; w == NULL: every weight
 // is 1
 template <int S>

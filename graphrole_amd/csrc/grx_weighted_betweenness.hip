@@ -32,8 +32,9 @@
 // Backward, level l = deepest .. 1, launched from the host: pull over the OUT-adjacency with its weights.  A cell at
 //   depth l adds sigma(v) * coeff(x) over its DAG successors x in arc order, each term networkx's own product; every
 //   successor is deeper, hence final.  Then coeff(v) = (1 + delta(v)) / sigma(v) replaces sigma(v).
-// Accumulation, endpoints and scale are those of grx_betweenness.hip: bc[v] adds the sources' contributions one after
-//   another in the caller's order (lanes in order, batches in order), the per-lane reach counts are integer adds, there
+// Accumulation, endpoints and scale are those of grx_betweenness.hip (grx_brandes.h, as are the argument checks and the
+//   per-batch sequence of these passes: br_open and br_run, which WbSide below serves): bc[v] adds the sources'
+//   contributions one after another in the caller's order (lanes in order, batches in order), the per-lane reach counts are integer adds, there
 //   are no floating-point atomics: the same bits for every S and every run.  The reach counts (needed with endpoints
 //   only) come from one pass over the depths after the forward loop.  MEASURED AND REMOVED: counting them inside the
 //   forward kernels with one atomicAdd per thread that resolved something, as grx_betweenness.hip does -- with S lanes
@@ -56,15 +57,12 @@
 #pragma clang fp contract(off)
 
 #include "grx_relax.h"
-#include "grx_edge_sum.h"
-
-#include <algorithm>
+#include "grx_brandes.h"
 
 namespace {
 
 constexpr int WB_BLOCK = 256;
-constexpr int WB_PARTS = 4;                                  // lane groups of a hub workgroup: the same for every S
-constexpr int WB_LEVEL_BATCH = 8;                            // forward rounds enqueued between two read-backs
+constexpr int WB_PARTS = BR_PARTS;                           // lane groups of a hub workgroup: the same for every S
 constexpr int WB_MAX_ROW_BLOCKS = 8192;
 constexpr int WB_MAX_BLOCKS = 2048;                           // grid of the per-element launches
 constexpr size_t WB_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of the library's choice of S
@@ -72,53 +70,39 @@ constexpr size_t WB_DEFAULT_STATE_BYTES = (size_t)4 << 30;   // state budget of 
 constexpr int32_t WB_OPEN = -1;                              // reached, depth not known yet
 constexpr int32_t WB_UNREACHED = -2;
 
-// D, delta, sigma (fp64) and depth (int32) per cell, the relaxation's stamp per node; grx_weighted_edge_betweenness
-// keeps coeff (fp64) in an array of its own
-size_t state_bytes(int64_t n, int S, bool keep_sigma)
-{
-    return (size_t)(n > 0 ? n : 1) * ((size_t)S * (keep_sigma ? 36 : 28) + 4);
-}
+// The workspace, laid out once: D, delta, sigma (fp64) and depth (int32) per (node, source) -- 28 bytes a cell; coeff
+// (fp64) in an array of its own for grx_weighted_edge_betweenness only, 36 bytes a cell (otherwise coeff replaces
+// sigma); the relaxation's stamp per node; the per-lane reach counts and the control words
+struct WbWs {
+    BrLayout lay;
+    double *D, *delta, *sigma, *coeff;
+    int32_t *depth, *stamp, *reach, *ctrl;
+    WbWs(void *base, int64_t n, int S, bool keep_sigma) : lay(base, n, S)
+    {
+        D = lay.per_cell<double>();
+        delta = lay.per_cell<double>();
+        sigma = lay.per_cell<double>();
+        coeff = keep_sigma ? lay.per_cell<double>() : nullptr;
+        depth = lay.per_cell<int32_t>();
+        stamp = lay.per_node<int32_t>();
+        reach = lay.take<int32_t>(S);
+        ctrl = lay.take<int32_t>(GRX_CTRL_MAX_WORDS);
+    }
+    size_t bytes() const { return lay.used; }
+};
 
 // batch = 0: the widest S whose state fits WB_DEFAULT_STATE_BYTES, never below 16 and no wider than the source list
 // rounded up
-int choose_batch(int64_t n, int batch, int64_t n_sources, bool keep_sigma = false)
+int choose_batch(int64_t n, int batch, int64_t n_sources, bool keep_sigma)
 {
     if (batch > 0) return batch;
+    const BrLayout lay = WbWs(nullptr, n, 1, keep_sigma).lay;
+    auto state_bytes = [&](int S) { return lay.nodes * ((size_t)S * lay.cell_bytes + lay.node_bytes); };
     int widest = 16;
-    while (widest < 64 && state_bytes(n, widest * 2, keep_sigma) <= WB_DEFAULT_STATE_BYTES) widest *= 2;
+    while (widest < 64 && state_bytes(widest * 2) <= WB_DEFAULT_STATE_BYTES) widest *= 2;
     int s = 16;
     while (s < widest && s < n_sources) s *= 2;
     return s;
-}
-
-size_t ws_bytes(int64_t n, int S, bool keep_sigma = false)
-{
-    const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)S;
-    return (keep_sigma ? 4 : 3) * grx_align_up(cells * 8, 256) + grx_align_up(cells * 4, 256) +
-           grx_align_up((size_t)(n > 0 ? n : 1) * 4, 256) + 256 + 256;
-}
-
-struct WbWs {
-    double *D, *delta, *sigma;
-    double *coeff;                                           // the edge entry point only; otherwise coeff replaces sigma
-    int32_t *depth, *stamp, *reach, *ctrl;
-};
-
-WbWs carve(void *base, int64_t n, int S, bool keep_sigma = false)
-{
-    const size_t cells = (size_t)(n > 0 ? n : 1) * (size_t)S;
-    char *p = reinterpret_cast<char *>(base);
-    WbWs ws;
-    ws.D = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
-    ws.delta = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
-    ws.sigma = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256);
-    ws.coeff = nullptr;
-    if (keep_sigma) { ws.coeff = reinterpret_cast<double *>(p); p += grx_align_up(cells * 8, 256); }
-    ws.depth = reinterpret_cast<int32_t *>(p); p += grx_align_up(cells * 4, 256);
-    ws.stamp = reinterpret_cast<int32_t *>(p); p += grx_align_up((size_t)(n > 0 ? n : 1) * 4, 256);
-    ws.reach = reinterpret_cast<int32_t *>(p); p += 256;
-    ws.ctrl = reinterpret_cast<int32_t *>(p);
-    return ws;
 }
 
 // the converged distances as depth marks: a cell with a path is open, one without (the unused lanes of a last, partial
@@ -271,7 +255,7 @@ __global__ __launch_bounds__(WB_PARTS * S) void wb_forward_hub_kernel(const int6
     __syncthreads();
     if (p != 0 || !open) return;
     if (!(clear[0][lane] && clear[1][lane] && clear[2][lane] && clear[3][lane])) return;
-    const double total = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+    const double total = br_combine4(part, lane);
     if (total > 0.0) {
         sigma[cell] = total;
         depth[cell] = l;
@@ -301,13 +285,6 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_reach_kernel(int64_t n, const int
     if (t < S && part[t]) atomicAdd(&reach[t], part[t]);
 }
 
-// networkx _accumulate_*: coeff = (1 + delta[w]) / sigma[w]; delta[v] += sigma[v] * coeff
-__device__ __forceinline__ void settle(int64_t cell, double d, double sv, double *coeff, double *__restrict__ delta)
-{
-    delta[cell] = d;
-    coeff[cell] = (1.0 + d) / sv;                            // coeff(v) for the shallower levels
-}
-
 // backward, level l: the cells at depth l pull delta from their DAG successors.  KEEP_SIGMA = false: coeff replaces
 // sigma in place (kept_coeff is not read); true: coeff goes to kept_coeff
 template <int S, bool KEEP_SIGMA>
@@ -327,7 +304,7 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_backward_kernel(int64_t n, const 
         const int64_t b = row_ptr[v], e = row_ptr[v + 1];
         if (e - b > hub_degree) continue;                   // wb_backward_hub_kernel
         const double sv = sigma[cell];
-        settle(cell, pull_succ<S>(b, e, 1, col, w, D, depth, coeff, lane, D[cell], l, sv), sv, coeff, delta);
+        br_settle(cell, pull_succ<S>(b, e, 1, col, w, D, depth, coeff, lane, D[cell], l, sv), sv, coeff, delta);
     }
 }
 
@@ -354,35 +331,7 @@ __global__ __launch_bounds__(WB_PARTS * S) void wb_backward_hub_kernel(const int
                          : 0.0;
     __syncthreads();
     if (p != 0 || !mine) return;
-    settle(cell, ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane], sv, coeff, delta);
-}
-
-// bc[v] += the contributions of the batch's sources in lane order (networkx: betweenness[w] += delta[w] for w != s;
-// with endpoints betweenness[s] += len(S) - 1 and betweenness[w] += delta[w] + 1)
-template <int S>
-__global__ __launch_bounds__(WB_BLOCK) void wb_accumulate_kernel(int64_t n, int count, int endpoints,
-                                                                 const int32_t *__restrict__ depth,
-                                                                 const double *__restrict__ delta,
-                                                                 const int32_t *__restrict__ reach,
-                                                                 double *__restrict__ bc)
-{
-    for (int64_t v = (int64_t)blockIdx.x * WB_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * WB_BLOCK) {
-        const int32_t *lv = depth + v * S;
-        const double *dv = delta + v * S;
-        double acc = bc[v];
-        for (int b = 0; b < count; ++b) {
-            const int l = lv[b];
-            if (l > 0) acc += endpoints ? dv[b] + 1.0 : dv[b];
-            else if (l == 0 && endpoints) acc += (double)(reach[b] - 1);
-        }
-        bc[v] = acc;
-    }
-}
-
-__global__ __launch_bounds__(WB_BLOCK) void wb_scale_kernel(int64_t n, double scale, double *__restrict__ bc)
-{
-    for (int64_t v = (int64_t)blockIdx.x * WB_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * WB_BLOCK)
-        bc[v] *= scale;
+    br_settle(cell, br_combine4(part, lane), sv, coeff, delta);
 }
 
 // grx_weighted_edge_betweenness, after the backward loop of a batch: the arcs [b, e) with stride `step` of row v, the
@@ -452,26 +401,29 @@ __global__ __launch_bounds__(WB_PARTS * S) void wb_edge_hub_kernel(const int64_t
     edge_row<S>(v, row_ptr[v] + p, row_ptr[v + 1], WB_PARTS, col, w, D, depth, sigma, coeff, lane, base, ebc);
 }
 
-struct Args {
+// What br_run drives: the carved state of one call at batch width S.  EDGES = false is grx_weighted_betweenness, true is
+// grx_weighted_edge_betweenness (`endpoints` is 0 there)
+template <int S, bool EDGES>
+struct WbSide {
     int64_t n;
     SpPull out, in;                                          // backward pulls over `out`; relaxation and forward over `in`
-    const int32_t *sources;
-    int64_t n_sources;
+    bool directed;
     int endpoints;
-    double *bc;                                              // EDGES: ebc, one value per arc of `out`
-};
+    WbWs ws;
+    int64_t *rounds, *levels;                                // relaxation rounds summed, the deepest DAG level
+    hipStream_t st;
 
-// EDGES = false is grx_weighted_betweenness, true is grx_weighted_edge_betweenness (`endpoints` is 0 there)
-template <int S, bool EDGES>
-int run(const Args &a, const WbWs &ws, int64_t *rounds, int64_t *levels, hipStream_t st)
-{
-    const int64_t n = a.n, cells = n * S;
-    const unsigned row_blocks = grx_grid(n, WB_BLOCK / S, WB_MAX_ROW_BLOCKS);
-    const unsigned egrid = grx_grid(n, WB_BLOCK, WB_MAX_BLOCKS);
-    for (int64_t first = 0; first < a.n_sources; first += S) {
-        const int count = (int)std::min<int64_t>(S, a.n_sources - first);
-        int rc = sp_relax<S>(
-            a.in, a.sources + first, count, ws.D, ws.delta, ws.stamp, ws.ctrl,
+    unsigned row_blocks() const { return grx_grid(n, WB_BLOCK / S, WB_MAX_ROW_BLOCKS); }
+    static const char *forward_refusal()
+    {
+        return EDGES ? "grx_weighted_edge_betweenness: the forward pass did not end after %lld rounds"
+                     : "grx_weighted_betweenness: the forward pass did not end after %lld rounds";
+    }
+    int begin(const int32_t *d_src, int count) const
+    {
+        const int64_t cells = n * S;
+        const int rc = sp_relax<S>(
+            in, d_src, count, ws.D, ws.delta, ws.stamp, ws.ctrl,
             EDGES ? "grx_weighted_edge_betweenness: the relaxation did not end after %lld rounds (a negative or NaN "
                     "weight?)"
                   : "grx_weighted_betweenness: the relaxation did not end after %lld rounds (a negative or NaN weight?)",
@@ -479,54 +431,48 @@ int run(const Args &a, const WbWs &ws, int64_t *rounds, int64_t *levels, hipStre
         if (rc != GRX_OK) return rc;
         // both distance buffers hold the fixed point: ws.delta is free
         wb_depth_init_kernel<<<grx_grid(cells, WB_BLOCK, WB_MAX_BLOCKS), WB_BLOCK, 0, st>>>(cells, ws.D, ws.depth);
-        wb_source_init_kernel<S><<<1, GRX_WAVE, 0, st>>>(n, count, a.sources + first, ws.depth, ws.sigma, ws.reach,
-                                                         ws.ctrl);
-        GRX_LAUNCH_CHECK();
-        int32_t h[2];
-        // a DAG over n nodes is at most n - 1 arcs deep; one more round finds that nothing resolves
-        rc = grx_run_rounds(
-            EDGES ? "grx_weighted_edge_betweenness: the forward pass did not end after %lld rounds"
-                  : "grx_weighted_betweenness: the forward pass did not end after %lld rounds",
-            WB_LEVEL_BATCH, n + 1, 2, ws.ctrl, h, st, [&] {
-                GRX_PROF(GRX_K_WBC_FORWARD, st);
-                if (a.in.n_hub_rows)
-                    wb_forward_hub_kernel<S><<<(unsigned)a.in.n_hub_rows, WB_PARTS * S, 0, st>>>(
-                        a.in.row_ptr, a.in.col, a.in.w, a.in.hub_rows, ws.D, ws.depth, ws.sigma, ws.ctrl);
-                wb_forward_kernel<S><<<row_blocks, WB_BLOCK, 0, st>>>(n, a.in.row_ptr, a.in.col, a.in.w,
-                                                                      a.in.hub_degree, ws.D, ws.depth, ws.sigma,
-                                                                      ws.ctrl);
-                return grx_frontier_advance(ws.ctrl, st);
-            });
-        if (rc != GRX_OK) return rc;
-        *levels = std::max<int64_t>(*levels, h[GRX_CT_LEVEL]);
-        if (a.endpoints)
-            wb_reach_kernel<S><<<grx_grid(n, WB_BLOCK / S, WB_MAX_BLOCKS), WB_BLOCK, 0, st>>>(n, ws.depth, ws.reach);
-        for (int l = h[GRX_CT_LEVEL]; l >= 1; --l) {        // deepest level first; the sources need no delta
-            GRX_PROF(GRX_K_WBC_BACKWARD, st);
-            if (a.out.n_hub_rows)
-                wb_backward_hub_kernel<S, EDGES><<<(unsigned)a.out.n_hub_rows, WB_PARTS * S, 0, st>>>(
-                    a.out.row_ptr, a.out.col, a.out.w, a.out.hub_rows, l, ws.D, ws.depth, ws.sigma, ws.coeff, ws.delta);
-            wb_backward_kernel<S, EDGES><<<row_blocks, WB_BLOCK, 0, st>>>(n, a.out.row_ptr, a.out.col, a.out.w,
-                                                                          a.out.hub_degree, l, ws.D, ws.depth, ws.sigma,
-                                                                          ws.coeff, ws.delta);
-            GRX_LAUNCH_CHECK();
-        }
-        if (EDGES) {
-            if (a.out.n_hub_rows)
-                wb_edge_hub_kernel<S><<<(unsigned)a.out.n_hub_rows, WB_PARTS * S, 0, st>>>(
-                    a.out.row_ptr, a.out.col, a.out.w, a.out.hub_rows, ws.D, ws.depth, ws.sigma, ws.coeff, a.bc);
-            wb_edge_kernel<S><<<row_blocks, WB_BLOCK, 0, st>>>(n, a.out.row_ptr, a.out.col, a.out.w, a.out.hub_degree,
-                                                               ws.D, ws.depth, ws.sigma, ws.coeff, a.bc);
-        } else {
-            wb_accumulate_kernel<S><<<egrid, WB_BLOCK, 0, st>>>(n, count, a.endpoints, ws.depth, ws.delta, ws.reach,
-                                                                a.bc);
-        }
-        GRX_LAUNCH_CHECK();
+        wb_source_init_kernel<S><<<1, GRX_WAVE, 0, st>>>(n, count, d_src, ws.depth, ws.sigma, ws.reach, ws.ctrl);
+        return GRX_OK;
     }
-    return GRX_OK;
-}
+    int forward_round() const
+    {
+        GRX_PROF(GRX_K_WBC_FORWARD, st);
+        if (in.n_hub_rows)
+            wb_forward_hub_kernel<S><<<(unsigned)in.n_hub_rows, WB_PARTS * S, 0, st>>>(
+                in.row_ptr, in.col, in.w, in.hub_rows, ws.D, ws.depth, ws.sigma, ws.ctrl);
+        wb_forward_kernel<S><<<row_blocks(), WB_BLOCK, 0, st>>>(n, in.row_ptr, in.col, in.w, in.hub_degree, ws.D,
+                                                                ws.depth, ws.sigma, ws.ctrl);
+        return grx_frontier_advance(ws.ctrl, st);
+    }
+    void after_forward(int deepest) const
+    {
+        *levels = std::max<int64_t>(*levels, deepest);
+        if (endpoints)
+            wb_reach_kernel<S><<<grx_grid(n, WB_BLOCK / S, WB_MAX_BLOCKS), WB_BLOCK, 0, st>>>(n, ws.depth, ws.reach);
+    }
+    void backward(int l) const
+    {
+        GRX_PROF(GRX_K_WBC_BACKWARD, st);
+        if (out.n_hub_rows)
+            wb_backward_hub_kernel<S, EDGES><<<(unsigned)out.n_hub_rows, WB_PARTS * S, 0, st>>>(
+                out.row_ptr, out.col, out.w, out.hub_rows, l, ws.D, ws.depth, ws.sigma, ws.coeff, ws.delta);
+        wb_backward_kernel<S, EDGES><<<row_blocks(), WB_BLOCK, 0, st>>>(n, out.row_ptr, out.col, out.w, out.hub_degree,
+                                                                        l, ws.D, ws.depth, ws.sigma, ws.coeff,
+                                                                        ws.delta);
+    }
+    void edge_pass(double *d_ebc) const
+    {
+        if (out.n_hub_rows)
+            wb_edge_hub_kernel<S><<<(unsigned)out.n_hub_rows, WB_PARTS * S, 0, st>>>(
+                out.row_ptr, out.col, out.w, out.hub_rows, ws.D, ws.depth, ws.sigma, ws.coeff, d_ebc);
+        wb_edge_kernel<S><<<row_blocks(), WB_BLOCK, 0, st>>>(n, out.row_ptr, out.col, out.w, out.hub_degree, ws.D,
+                                                             ws.depth, ws.sigma, ws.coeff, d_ebc);
+    }
+    const int32_t *level() const { return ws.depth; }
+    int stride() const { return S; }
+};
 
-// the argument checks and the batches of both entry points
+// the argument checks and the batches of both entry points (d_out = bc resp. ebc)
 template <bool EDGES>
 int entry(const char *name, int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
           const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr,
@@ -535,52 +481,27 @@ int entry(const char *name, int64_t n, const int64_t *d_row_ptr, const int32_t *
           double *d_out, int64_t *h_rounds, int64_t *h_levels, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     GRX_REQUIRE(batch == 0 || sp_valid_batch(batch), "%s: batch must be 0, 16, 32 or 64 (got %d)", name, batch);
-    GRX_REQUIRE(n > 0 && n < (int64_t)1 << 31, "%s: n = %lld out of range", name, (long long)n);
-    GRX_REQUIRE(d_row_ptr && d_col && d_out && d_workspace, "%s: null pointer", name);
-    GRX_REQUIRE(n_sources >= 0 && n_sources < (int64_t)1 << 31 && (n_sources == 0 || d_sources), "%s: source list",
-                name);
-    const bool directed = d_in_row_ptr != nullptr;
-    GRX_REQUIRE(!directed || d_in_col, "%s: d_in_col is required with d_in_row_ptr", name);
-    GRX_REQUIRE(!directed || (d_w == nullptr) == (d_in_w == nullptr),
-                "%s: d_w and d_in_w must both be given or both be NULL", name);
-    if (!directed) {                                         // undirected: the CSR is its own in-adjacency
-        d_in_row_ptr = d_row_ptr;
-        d_in_col = d_col;
-        d_in_w = d_w;
-        d_in_hub_rows = d_hub_rows;
-        n_in_hub_rows = n_hub_rows;
-        in_lanes_per_row = lanes_per_row;
-    }
-    GRX_REQUIRE(lanes_per_row >= 1 && in_lanes_per_row >= 1, "%s: lanes_per_row must be >= 1", name);
-    GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows) && n_in_hub_rows >= 0 &&
-                    (n_in_hub_rows == 0 || d_in_hub_rows), "%s: hub list", name);
+    GRX_REQUIRE(n_sources < (int64_t)1 << 31, "%s: source list", name);
     const int S = choose_batch(n, batch, n_sources, EDGES);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, S, EDGES), "%s: workspace %zu bytes, need %zu", name, workspace_bytes,
-                ws_bytes(n, S, EDGES));
+    const WbWs ws(d_workspace, n, S, EDGES);
+    SpPull out, in;
+    bool directed;
+    int rc = br_open(name, n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows, lanes_per_row, d_in_row_ptr, d_in_col,
+                     d_in_w, d_in_hub_rows, n_in_hub_rows, in_lanes_per_row, d_sources, n_sources, d_out, d_workspace,
+                     workspace_bytes, ws.bytes(), out, in, directed);
+    if (rc != GRX_OK) return rc;
+    GRX_REQUIRE((out.w == nullptr) == (in.w == nullptr), "%s: d_w and d_in_w must both be given or both be NULL", name);
     hipStream_t st = grx_stream(stream);
-    const WbWs ws = carve(d_workspace, n, S, EDGES);
-    const Args a{n,
-                 SpPull{n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row},
-                 SpPull{n, d_in_row_ptr, d_in_col, d_in_w, d_in_hub_rows, n_in_hub_rows,
-                        (int64_t)GRX_HUB_FACTOR * in_lanes_per_row},
-                 d_sources, n_sources, endpoints, d_out};
-    if (EDGES) eb_rows<EB_ZERO>(n, d_row_ptr, d_col, 0.0, d_out, st);
-    else grx_fill64(reinterpret_cast<uint64_t *>(d_out), n, 0, st);
-    GRX_LAUNCH_CHECK();
     int64_t rounds = 0, levels = 0;
-    int rc;
+    auto run = [&](auto side) { return br_run<EDGES>(side, d_sources, n_sources, endpoints, scale, d_out, st); };
     switch (S) {
-    case 16: rc = run<16, EDGES>(a, ws, &rounds, &levels, st); break;
-    case 32: rc = run<32, EDGES>(a, ws, &rounds, &levels, st); break;
-    default: rc = run<64, EDGES>(a, ws, &rounds, &levels, st); break;
+    case 16: rc = run(WbSide<16, EDGES>{n, out, in, directed, endpoints, ws, &rounds, &levels, st}); break;
+    case 32: rc = run(WbSide<32, EDGES>{n, out, in, directed, endpoints, ws, &rounds, &levels, st}); break;
+    default: rc = run(WbSide<64, EDGES>{n, out, in, directed, endpoints, ws, &rounds, &levels, st}); break;
     }
     if (h_rounds) *h_rounds = rounds;
     if (h_levels) *h_levels = levels;
-    if (rc != GRX_OK) return rc;
-    if (EDGES) eb_finish(n, d_row_ptr, d_col, directed, scale, d_out, st);
-    else wb_scale_kernel<<<grx_grid(n, WB_BLOCK, WB_MAX_BLOCKS), WB_BLOCK, 0, st>>>(n, scale, d_out);
-    GRX_LAUNCH_CHECK();
-    return GRX_OK;
+    return rc;
 }
 
 }  // namespace
@@ -589,7 +510,7 @@ extern "C" {
 
 size_t grx_weighted_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources)
 {
-    return ws_bytes(n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources));
+    return WbWs(nullptr, n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources, false), false).bytes();
 }
 
 int grx_weighted_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
@@ -608,7 +529,7 @@ int grx_weighted_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t 
 
 size_t grx_weighted_edge_betweenness_workspace_bytes(int64_t n, int batch, int64_t n_sources)
 {
-    return ws_bytes(n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources, true), true);
+    return WbWs(nullptr, n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources, true), true).bytes();
 }
 
 int grx_weighted_edge_betweenness(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,

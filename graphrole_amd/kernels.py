@@ -44,6 +44,8 @@ WB_MAX_ROW_BLOCKS = 8192     # workgroups of the row kernels (256 / batch rows e
 WB_MAX_BLOCKS = 2048         # and of the per-element launches
 BW_BLOCK = 256               # csrc/grx_betweenness.hip: threads per workgroup,
 BW_MAX_ROW_BLOCKS = 1024     # workgroups of the row kernels (4 rows each: one wavefront per row), the edge pass among them
+BR_BLOCK = 256               # csrc/grx_brandes.h (the four betweenness entry points): threads per workgroup
+BR_MAX_BLOCKS = 2048         # and workgroups of the per-node accumulation and scale launches
 EB_BLOCK = 256               # csrc/grx_edge_sum.h (grx_edge_betweenness, grx_weighted_edge_betweenness): threads per
 EB_ROW_LANES = 16            # workgroup and lanes per row of the passes that zero and finish the arc slots,
 EB_MAX_ROW_BLOCKS = 2048     # and their workgroups (256 / 16 rows each)
@@ -1224,6 +1226,15 @@ def _workspace(symbol: str, *args) -> Tuple[torch.Tensor, int]:
     return torch.empty(nbytes, dtype=torch.uint8, device=device()), nbytes
 
 
+def _brandes_head(symbol: str, n: int, sources: np.ndarray, batch: int,
+                  out_len: int) -> Tuple[torch.Tensor, torch.Tensor, int, torch.Tensor]:
+    """What the four betweenness wrappers begin with: (int32 device sources, workspace of `symbol`_workspace_bytes for
+    the batch width the call uses, its size, fp64[out_len] output)."""
+    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
+    ws, ws_bytes = _workspace(symbol + '_workspace_bytes', n, int(batch), len(src))
+    return src, ws, ws_bytes, torch.empty(max(out_len, 1), dtype=torch.float64, device=device())
+
+
 def _power(name: str, csr_in: DeviceCSR, out_weight: Optional[torch.Tensor], alpha: float, tol: float,
            max_iter: int, lanes: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     n = csr_in.n
@@ -1311,9 +1322,7 @@ def betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: np.nda
     out-adjacency csr_out and the in-adjacency csr_in (None for an undirected graph); bc multiplied by `scale`.
     batch = sources per batch (a multiple of 64; 0 = the library's choice)."""
     n = csr_out.n
-    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
-    ws, ws_bytes = _workspace('grx_betweenness_workspace_bytes', n, int(batch), len(src))   # for the B the call uses
-    bc = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    src, ws, ws_bytes, bc = _brandes_head('grx_betweenness', n, sources, batch, n)
     _lib.call('grx_betweenness', n, *_csr_args(csr_out), *_csr_args(csr_in), _ptr(src), len(src), int(bool(endpoints)),
               float(scale), int(batch), _ptr(bc), _ptr(ws), ws_bytes, _stream())
     return bc
@@ -1396,9 +1405,7 @@ def weighted_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], source
     per batch (16, 32 or 64; 0 = the library's choice).  (bc fp64[n], relaxation rounds summed over the batches, the
     deepest level of the shortest-path DAG)."""
     n = csr_out.n
-    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
-    ws, ws_bytes = _workspace('grx_weighted_betweenness_workspace_bytes', n, int(batch), len(src))
-    bc = torch.empty(max(n, 1), dtype=torch.float64, device=device())
+    src, ws, ws_bytes, bc = _brandes_head('grx_weighted_betweenness', n, sources, batch, n)
     rounds, levels = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.call('grx_weighted_betweenness', n, *_weighted_csr_args(csr_out), *_weighted_csr_args(csr_in), _ptr(src),
               len(src), int(bool(endpoints)), float(scale), int(batch), _ptr(bc), ctypes.byref(rounds),
@@ -1413,9 +1420,7 @@ def edge_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], sources: n
     of csr_out, multiplied by `scale`; both arcs of an undirected edge hold the edge's value.  batch = sources per batch
     (a multiple of 64; 0 = the library's choice)."""
     n = csr_out.n
-    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
-    ws, ws_bytes = _workspace('grx_edge_betweenness_workspace_bytes', n, int(batch), len(src))
-    ebc = torch.empty(max(csr_out.nnz, 1), dtype=torch.float64, device=device())
+    src, ws, ws_bytes, ebc = _brandes_head('grx_edge_betweenness', n, sources, batch, csr_out.nnz)
     _lib.call('grx_edge_betweenness', n, *_csr_args(csr_out), *_csr_args(csr_in), _ptr(src), len(src), float(scale),
               int(batch), _ptr(ebc), _ptr(ws), ws_bytes, _stream())
     return ebc
@@ -1427,9 +1432,7 @@ def weighted_edge_betweenness(csr_out: DeviceCSR, csr_in: Optional[DeviceCSR], s
     ``weighted_betweenness`` without `endpoints`.  (ebc fp64[nnz] as ``edge_betweenness``, relaxation rounds summed
     over the batches, the deepest level of the shortest-path DAG).  batch = 16, 32 or 64; 0 = the library's choice."""
     n = csr_out.n
-    src = torch.from_numpy(np.ascontiguousarray(sources, dtype=np.int32)).to(device())
-    ws, ws_bytes = _workspace('grx_weighted_edge_betweenness_workspace_bytes', n, int(batch), len(src))
-    ebc = torch.empty(max(csr_out.nnz, 1), dtype=torch.float64, device=device())
+    src, ws, ws_bytes, ebc = _brandes_head('grx_weighted_edge_betweenness', n, sources, batch, csr_out.nnz)
     rounds, levels = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.call('grx_weighted_edge_betweenness', n, *_weighted_csr_args(csr_out), *_weighted_csr_args(csr_in), _ptr(src),
               len(src), float(scale), int(batch), _ptr(ebc), ctypes.byref(rounds), ctypes.byref(levels), _ptr(ws),

@@ -300,11 +300,15 @@ def test_ctypes_signatures_header_and_caps():
     csrc = os.path.join(ROOT, 'graphrole_amd', 'csrc')
     shared = open(os.path.join(csrc, 'grx_edge_sum.h')).read()
     assert '#pragma clang fp contract(off)' in shared
+    brandes = open(os.path.join(csrc, 'grx_brandes.h')).read()   # what both files include grx_edge_sum.h through
+    assert '#include "grx_edge_sum.h"' in brandes and '#pragma clang fp contract(off)' in brandes
+    assert 'atomicAdd(&ebc' not in brandes and 'unsafeAtomicAdd' not in brandes
     for name in ('grx_betweenness.hip', 'grx_weighted_betweenness.hip'):
         text = open(os.path.join(csrc, name)).read()
-        assert '#include "grx_edge_sum.h"' in text and '#pragma clang fp contract(off)' in text
+        assert '#include "grx_brandes.h"' in text and '#pragma clang fp contract(off)' in text
         assert 'atomicAdd(&ebc' not in text and 'unsafeAtomicAdd' not in text
-    assert 'grx_edge_sum.h' in open(os.path.join(csrc, 'Makefile')).read()
+    makefile = open(os.path.join(csrc, 'Makefile')).read()
+    assert 'grx_edge_sum.h' in makefile and 'grx_brandes.h' in makefile
     # the caps the second-trip test sizes itself by are the ones in the sources
     for text, constant in ((shared, 'EB_BLOCK'), (shared, 'EB_ROW_LANES'), (shared, 'EB_MAX_ROW_BLOCKS'),
                            (open(os.path.join(csrc, 'grx_betweenness.hip')).read(), 'BW_BLOCK'),

@@ -155,6 +155,41 @@ def test_same_bits_for_every_batch_and_run(key):
     assert _batched(G, 64, k=70, seed=5).tobytes() == sampled.tobytes()
 
 
+def _hub_graph(directed):
+    """300 nodes: a sparse random graph and a star centre whose row is a hub row (node 0 -> 1 .. 250; in the digraph
+    also 40 .. 289 -> 299, so that the in-adjacency has a hub row of its own)."""
+    G = nx.gnm_random_graph(300, 900, seed=21, directed=directed)
+    G.add_edges_from((0, v) for v in range(1, 251))
+    if directed:
+        G.add_edges_from((v, 299) for v in range(40, 290))
+    return G
+
+
+@pytest.mark.parametrize('directed', [False, True], ids=['undirected', 'directed'])
+def test_same_bits_with_endpoints_a_hub_row_and_a_repeated_source(directed):
+    """The accumulation every batch width shares: `endpoints`, 70 sources (64 + 6 lanes at width 64, one partial batch at
+    the wider ones), one node the source of two lanes, hub rows in both passes."""
+    from networkx.algorithms.centrality import betweenness as nxb
+    from graphrole_amd import kernels as K
+    from graphrole_amd.graph.interface.networkx import NetworkxInterface
+    G = _hub_graph(directed)
+    host, out, tr = NetworkxInterface(G)._device_graph()
+    assert out.n_hubs > 0 and (tr.n_hubs > 0 if directed else tr is None)
+    labels = sorted(G)
+    picks = np.random.default_rng(4).permutation(len(labels))[:69]
+    picks = np.append(picks, picks[0])                           # 70: shuffled, a repeat
+    want = dict.fromkeys(G, 0.0)
+    for p in picks:                                              # networkx's own loops over this source list
+        S, P, sigma, _ = nxb._single_source_shortest_path_basic(G, labels[p])
+        want, _ = nxb._accumulate_endpoints(want, S, P, sigma, labels[p])
+    inv = np.asarray(host.inv)
+    runs = [K.to_host(K.betweenness(out, tr, inv[picks], True, 0.25, batch=batch))[:host.n]
+            for batch in (64, 128, 192, 256, 0, 64)]
+    for got in runs[1:]:                                         # every width, and width 64 a second time
+        assert got.tobytes() == runs[0].tobytes()
+    np.testing.assert_allclose(runs[0][inv], [0.25 * want[v] for v in labels], rtol=bo.RTOL, atol=0)
+
+
 def test_sampled_sources_follow_networkx():
     from graphrole_amd import betweenness_centrality, kernels
     G = nx.relabel_nodes(nx.barabasi_albert_graph(1000, 3, seed=9), lambda v: f'v{v:04d}')

@@ -244,7 +244,7 @@ def test_weighted_betweenness(kind):
     assert sources.max() > ROWS and len(set((sources % C).tolist())) == 3
     hub_out = K.HUB_FACTOR * small.lanes_per_row
     hub_in = K.HUB_FACTOR * (small_in if directed else small).lanes_per_row
-    assert _wraps(n, K.WB_BLOCK, K.WB_MAX_BLOCKS)                               # wb_accumulate, wb_scale
+    assert _wraps(n, K.BR_BLOCK, K.BR_MAX_BLOCKS)                               # br_accumulate, br_scale
 
     def device(csr, csr_in, rows, endpoints, batch):
         bc, rounds, levels = K.weighted_betweenness(csr, csr_in, rows, endpoints, 0.25, batch)

@@ -45,7 +45,7 @@ def test_the_batches_are_the_ones_of_the_sources():
     def constant(file, name):
         return int(re.search(rf'constexpr int {name} = (\d+);', (CSRC / file).read_text()).group(1))
 
-    assert constant('grx_betweenness.hip', 'BW_LEVEL_BATCH') == rl.LEVEL_BATCH
+    assert constant('grx_brandes.h', 'BR_LEVEL_BATCH') == rl.LEVEL_BATCH     # all four betweenness entry points
     assert constant('grx_closeness.hip', 'CL_LEVEL_BATCH') == rl.LEVEL_BATCH
     assert constant('grx_biconnected.hip', 'BC_LEVEL_BATCH') == rl.LEVEL_BATCH
     assert constant('grx_kcore.hip', 'KC_ROUND_BATCH') == rl.ROUND_BATCH

@@ -228,6 +228,8 @@ CAPS = {
     'grx_relax.h': ('SP_BLOCK', 'SP_MAX_ROW_BLOCKS'),
     'grx_sssp.hip': ('SP_MAX_BLOCKS',),
     'grx_weighted_betweenness.hip': ('WB_BLOCK', 'WB_MAX_ROW_BLOCKS', 'WB_MAX_BLOCKS'),
+    'grx_betweenness.hip': ('BW_BLOCK', 'BW_MAX_ROW_BLOCKS'),
+    'grx_brandes.h': ('BR_BLOCK', 'BR_MAX_BLOCKS'),
     'grx_closeness.hip': ('CL_BLOCK', 'CL_MAX_ROW_BLOCKS'),
     'grx_neighbor_sense.hip': ('NS_BLOCK', 'NS_MAX_WG', 'NS_LONG_MAX_WG', 'NS_LONG_ROW'),
     'grx_rowjoin.h': ('RJ_BLOCK', 'RJ_ROW_MAX_WG', 'RJ_ARC_MAX_WG'),
@@ -248,9 +250,11 @@ LAUNCHES = {
     'grx_relax.h': ('grx_grid(n, SP_BLOCK / S, SP_MAX_ROW_BLOCKS)',),
     'grx_sssp.hip': ('grx_grid(n, SP_BLOCK, SP_MAX_BLOCKS)', 'grx_grid(n, SP_BLOCK / S, SP_MAX_BLOCKS)',
                      'grx_grid(n, GRX_WAVE, SP_MAX_BLOCKS)'),
-    'grx_weighted_betweenness.hip': ('grx_grid(n, WB_BLOCK / S, WB_MAX_ROW_BLOCKS)', 'grx_grid(n, WB_BLOCK, WB_MAX_BLOCKS)',
+    'grx_weighted_betweenness.hip': ('grx_grid(n, WB_BLOCK / S, WB_MAX_ROW_BLOCKS)',
                                      'grx_grid(cells, WB_BLOCK, WB_MAX_BLOCKS)',
                                      'grx_grid(n, WB_BLOCK / S, WB_MAX_BLOCKS)'),
+    'grx_betweenness.hip': ('grx_grid(n, BW_WAVES, BW_MAX_ROW_BLOCKS)', 'grx_grid(cells, BW_BLOCK, BW_MAX_BLOCKS)'),
+    'grx_brandes.h': ('grx_grid(n, BR_BLOCK, BR_MAX_BLOCKS)',),     # the accumulation and the scale of all four entries
     'grx_closeness.hip': ('grx_grid(n, CL_BLOCK / W, CL_MAX_ROW_BLOCKS)',    # the one level launch of the three users
                           'grx_grid(a.n, CL_BLOCK, CL_MAX_BLOCKS)'),         # grx_distance_sums' per-node rounding
     'grx_neighbor_sense.hip': ('grx_grid(A.n, NS_BLOCK / (S * CL), NS_MAX_WG)',

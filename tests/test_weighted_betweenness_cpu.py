@@ -354,6 +354,7 @@ def test_ctypes_signatures_and_header():
     assert '#define GRX_VERSION 1100' in header
     source = open(os.path.join(ROOT, 'graphrole_amd', 'csrc', 'grx_weighted_betweenness.hip')).read()
     assert '#pragma clang fp contract(off)' in source and '#include "grx_relax.h"' in source
+    assert '#include "grx_brandes.h"' in source
     assert '#include "grx_relax.h"' in open(os.path.join(ROOT, 'graphrole_amd', 'csrc', 'grx_sssp.hip')).read()
     assert 'grx_weighted_betweenness.hip' in open(os.path.join(ROOT, 'graphrole_amd', 'csrc', 'Makefile')).read()
 
