@@ -3,10 +3,10 @@
 // The reference quantises all entries of a factor matrix with sklearn KMeans(n_clusters=n_bins,
 // random_state=1) on the flattened values ("Lloyd-Max quantizer which can be computed using
 // kmeans", factor.py:38-39).  k-means++ seeding from a host RNG cannot be reproduced on a device,
-// so parity is by property: <= n_bins distinct output values, every value is
-// replaced by the mean of its cell, cells are nearest-centre cells, and the quantisation error is
-// not worse than sklearn's.  To meet the last point deterministically the start is not random:
-//   1. sort the values (batched radix sort of grx_sort.hip), prefix sums of s, s^2 and of
+// so parity is by property and against tests/lloyd_max_oracle.py: <= n_bins distinct
+// output values, every value is replaced by the mean of its cell, cells are nearest-centre cells, and the
+// quantisation error is not worse than sklearn's.  To meet the last point deterministically the start is not random:
+//   1. sort the values (batched radix sort of grx_sort.hip), prefix sums of s - pivot, (s - pivot)^2 and of
 //      cbrt(gap)^2 (Panter-Dite: optimal cell density ~ pdf^(1/3))
 //   2. cut the sorted values into <= 1024 micro-cells of equal cbrt-density mass (or one value per
 //      cell when there are few values) and solve the k-cluster problem on the cells EXACTLY by
@@ -14,7 +14,12 @@
 //   3. refine with Lloyd iterations on the full sorted array (cluster sums from the prefix sums:
 //      O(k log m) per iteration) until no boundary moves
 //   4. map every input value to its cell centre.
-// With <= 1024 values step 2 is the exact optimum of the k-means objective (<= any k-means run).
+// With <= 8192 values every value is its own cell and step 2 is the optimum of the k-means objective (<= any
+// k-means run) up to the rounding of the prefix sums.  Those are sums of s - pivot and (s - pivot)^2 with
+// pivot = sorted[m / 2], read from the sorted array by every kernel that needs it: the cluster cost
+// (P2[b] - P2[a]) - (P[b] - P[a])^2 / n does not depend on the pivot, its rounding error scales with
+// sum (s - pivot)^2 instead of sum s^2, and a centre is pivot + (P[b] - P[a]) / n -- so translating the input
+// translates the result (tests/lloyd_max_oracle.py states the bound and is the twin the kernels are tested against).
 #include "grx_common.h"
 
 namespace {
@@ -25,13 +30,14 @@ constexpr int Q_MAX_BINS = 256;          // exact-DP start + one-thread-per-clus
 constexpr int QC_BIG = 8192;             // exact DP with one cell per value up to this many values
 constexpr int Q_BIG_MAX_BINS = 65536;    // above Q_MAX_BINS: companding start, strided Lloyd kernel, tables in global memory
 
-// ---- three fused prefix sums over the sorted values: s, s^2, cbrt(s[i+1]-s[i])^2 -----------
+// ---- three fused prefix sums over the sorted values: s - pivot, (s - pivot)^2, cbrt(s[i+1]-s[i])^2 -----------
 __device__ __forceinline__ void q_terms(const double *__restrict__ s, int64_t m, int64_t i, double &a, double &b,
                                         double &c)
 {
     const double x = s[i];
-    a = x;
-    b = x * x;
+    const double d = x - s[m >> 1];
+    a = d;
+    b = d * d;
     const double gap = (i + 1 < m) ? (s[i + 1] - x) : 0.0;
     const double r = cbrt(gap);
     c = r * r;
@@ -229,12 +235,13 @@ __global__ __launch_bounds__(Q_MAX_BINS) void q_lloyd_kernel(const double *__res
     __shared__ int64_t hi[Q_MAX_BINS + 1];
     __shared__ int live[Q_MAX_BINS];
     const int j = threadIdx.x;
+    const double pivot = s[m >> 1];                     // P sums s - pivot
     if (j == 0) hi[0] = 0;
     if (j < k) {
         const int64_t a = edges[j], b = edges[j + 1];
         hi[j + 1] = b;
         live[j] = b > a;
-        c[j] = (b > a) ? (P[b] - P[a]) / (double)(b - a) : 0.0;
+        c[j] = (b > a) ? pivot + (P[b] - P[a]) / (double)(b - a) : 0.0;
     }
     __syncthreads();
     // empty clusters (fewer distinct cells than bins) inherit the centre below them
@@ -256,7 +263,7 @@ __global__ __launch_bounds__(Q_MAX_BINS) void q_lloyd_kernel(const double *__res
         __syncthreads();
         if (j < k) {
             const int64_t a = hi[j], b = hi[j + 1];
-            if (b > a) c[j] = (P[b] - P[a]) / (double)(b - a);
+            if (b > a) c[j] = pivot + (P[b] - P[a]) / (double)(b - a);
         }
         __syncthreads();
     }
@@ -334,10 +341,11 @@ __global__ __launch_bounds__(1024) void q_lloyd_big_kernel(const double *__restr
                                                            double *__restrict__ bounds, int32_t *__restrict__ info)
 {
     const int t = threadIdx.x, nt = blockDim.x;
+    const double pivot = s[m >> 1];                        // P sums s - pivot
     for (int j = t; j < k; j += nt) {
         const int64_t a = edges[j], b = edges[j + 1];
         hi[j + 1] = b;
-        c[j] = (b > a) ? (P[b] - P[a]) / (double)(b - a) : -1e308;      // marker: empty
+        c[j] = (b > a) ? pivot + (P[b] - P[a]) / (double)(b - a) : -1e308;      // marker: empty
     }
     if (t == 0) hi[0] = 0;
     __syncthreads();
@@ -369,7 +377,7 @@ __global__ __launch_bounds__(1024) void q_lloyd_big_kernel(const double *__restr
         __syncthreads();
         for (int j = t; j < k; j += nt) {
             const int64_t a = hi[j], b = hi[j + 1];
-            if (b > a) c[j] = (P[b] - P[a]) / (double)(b - a);
+            if (b > a) c[j] = pivot + (P[b] - P[a]) / (double)(b - a);
         }
         __syncthreads();
     }

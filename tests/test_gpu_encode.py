@@ -4,8 +4,9 @@ KMeans(n_clusters, random_state=1) on the flattened entries).
   * quantizer='kmeans' (default, grx_kmeans1d): the same procedure -- seeding draws of RandomState(1), Lloyd
     iterations, stopping rule, empty-cluster relocation -- compared NUMERICALLY with sklearn run here: equal
     iteration count, equal number of distinct levels, every quantised value within 1e-9.
-  * quantizer='lloyd_max' (grx_lloyd_max): parity by property (SURVEY.md 8f-1): <= n_bins distinct values;
-    Lloyd-Max fixed-point conditions; quantisation error not above sklearn's; the exact optimum on small inputs.
+  * quantizer='lloyd_max' (grx_lloyd_max): parity by property and against tests/lloyd_max_oracle.py
+    (stage by stage: tests/test_gpu_lloyd_max.py): <= n_bins distinct values; Lloyd-Max fixed-point conditions;
+    quantisation error not above sklearn's; the exact optimum (the oracle's DP) on small inputs.
 """
 import warnings
 
@@ -83,25 +84,14 @@ def test_lloyd_max_properties_and_error_vs_sklearn(case):
 def test_lloyd_max_small_input_is_the_exact_optimum():
     """<= 1024 values: the DP stage sees every value, so the result is the global k-means optimum."""
     from graphrole_amd.roles import factor
+    from tests import lloyd_max_oracle
     rng = np.random.RandomState(3)
     for m, k in [(12, 3), (60, 32), (200, 7), (1000, 16)]:
         data = np.sort(rng.lognormal(0, 1.5, m))
         q = factor.encode(data.reshape(1, -1), k, quantizer='lloyd_max').ravel()
         got = float(((data - q) ** 2).sum())
-        # brute-force DP over the sorted values
-        P = np.concatenate([[0.0], np.cumsum(data)])
-        P2 = np.concatenate([[0.0], np.cumsum(data * data)])
-        D = np.full(m + 1, np.inf)
-        D[0] = 0.0
-        for j in range(k):
-            new = np.full(m + 1, np.inf)
-            for i in range(j + 1, m + 1):
-                mm = np.arange(j, i)
-                n = i - mm
-                cost = (P2[i] - P2[mm]) - (P[i] - P[mm]) ** 2 / n
-                new[i] = np.min(D[mm] + np.maximum(cost, 0))
-            D = new
-        assert got <= D[m] * (1 + 1e-9) + 1e-12, (m, k, got, D[m])
+        optimum = float(lloyd_max_oracle.quantise(data, k, 0).dp_cost)   # long-double DP, one value per cell
+        assert got <= optimum * (1 + 1e-9) + 1e-12, (m, k, got, optimum)
 
 
 def test_encode_shape_errors_and_determinism():
