@@ -48,14 +48,6 @@ constexpr int BC_BINS = 1024;                                // levels counted i
 
 enum { CT_NCOMP = GRX_CT_BFS_WORDS, CT_COUNT };   // after the three words of the BFS loop
 
-size_t array_bytes(int64_t n) { return grx_align_up(((size_t)(n > 0 ? n : 1) + 2) * sizeof(int32_t), 256); }
-
-size_t ws_bytes(int64_t n)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1) + 2;
-    return 10 * array_bytes(n) + grx_align_up((nn / BC_SCAN_TILE + 2) * sizeof(int32_t), 256) + 256;
-}
-
 struct BcWs {
     int32_t *uf;                                             // component labels (1), then tree-edge labels (6)
     int32_t *level, *parent, *size, *pre, *low, *high;
@@ -66,17 +58,16 @@ struct BcWs {
     int32_t *ctrl;
 };
 
-BcWs carve(void *base, int64_t n)
+// ten arrays of n + 2 words, the tile sums, the control words
+BcWs lay_out(GrxCarve &c, int64_t n)
 {
-    char *p = reinterpret_cast<char *>(base);
-    const size_t a = array_bytes(n);
+    const size_t nn = (size_t)(n > 0 ? n : 1) + 2;
     BcWs ws;
     int32_t **arrays[] = {&ws.uf, &ws.level, &ws.parent, &ws.size, &ws.pre, &ws.low, &ws.high, &ws.order, &ws.offs,
                           &ws.top};
-    for (int32_t **f : arrays) { *f = reinterpret_cast<int32_t *>(p); p += a; }
-    ws.bsum = reinterpret_cast<int32_t *>(p);
-    p += grx_align_up((((size_t)(n > 0 ? n : 1) + 2) / BC_SCAN_TILE + 2) * sizeof(int32_t), 256);
-    ws.ctrl = reinterpret_cast<int32_t *>(p);
+    for (int32_t **f : arrays) *f = c.take<int32_t>(nn);
+    ws.bsum = c.take<int32_t>(nn / BC_SCAN_TILE + 2);
+    ws.ctrl = c.take<int32_t>(GRX_CTRL_MAX_WORDS);
     return ws;
 }
 
@@ -543,7 +534,7 @@ int scan_exclusive(int64_t m, int32_t *a, int32_t *bsum, hipStream_t st)
 
 extern "C" {
 
-size_t grx_biconnected_workspace_bytes(int64_t n) { return ws_bytes(n); }
+size_t grx_biconnected_workspace_bytes(int64_t n) { return grx_carve_bytes(lay_out, n); }
 
 int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                     int64_t n_hub_rows, int lanes_per_row, int64_t *d_count, int32_t *d_parent, int32_t *d_label,
@@ -553,10 +544,10 @@ int grx_biconnected(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
     GRX_REQUIRE(d_row_ptr && d_col && d_count && d_workspace, "grx_biconnected: null pointer");
     GRX_REQUIRE(lanes_per_row >= 1, "grx_biconnected: lanes_per_row must be >= 1");
     GRX_REQUIRE(n_hub_rows >= 0 && n_hub_rows <= n && (n_hub_rows == 0 || d_hub_rows), "grx_biconnected: hub list");
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n), "grx_biconnected: workspace %zu bytes, need %zu", workspace_bytes,
-                ws_bytes(n));
+    GrxCarve c(d_workspace);
+    const BcWs ws = lay_out(c, n);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_biconnected: workspace %zu bytes, need %zu", workspace_bytes, c.used);
     hipStream_t st = grx_stream(stream);
-    const BcWs ws = carve(d_workspace, n);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
     const unsigned egrid = grx_grid(n, BC_BLOCK, BC_MAX_BLOCKS), hubs = (unsigned)n_hub_rows;
     const unsigned lgrid = std::min<unsigned>(egrid, BC_LEVEL_BLOCKS);

@@ -79,20 +79,11 @@ __global__ __launch_bounds__(BR_BLOCK) void br_scale_kernel(int64_t n, double sc
         bc[v] *= scale;
 }
 
-// One walk over a workspace of `width` cells per node: every array starts on a 256-byte boundary.  base == NULL: only
-// the sizes are wanted.  `used` ends as the bytes of the workspace; cell_bytes and node_bytes are what one (node,
-// source) and one node cost, for a file's choice of the batch width.
-struct BrLayout {
-    char *base;
-    size_t nodes, width, used = 0, cell_bytes = 0, node_bytes = 0;
-    BrLayout(void *b, int64_t n, int w) : base(reinterpret_cast<char *>(b)), nodes(n > 0 ? n : 1), width(w) {}
-    template <class T>
-    T *take(size_t count)
-    {
-        T *at = base ? reinterpret_cast<T *>(base + used) : nullptr;
-        used += grx_align_up(count * sizeof(T), 256);
-        return at;
-    }
+// The walk (GrxCarve) over a workspace of `width` cells per node; cell_bytes and node_bytes are what one (node, source)
+// and one node cost, for a file's choice of the batch width.
+struct BrLayout : GrxCarve {
+    size_t nodes, width, cell_bytes = 0, node_bytes = 0;
+    BrLayout(void *b, int64_t n, int w) : GrxCarve(b), nodes(n > 0 ? n : 1), width(w) {}
     template <class T>
     T *per_cell() { cell_bytes += sizeof(T); return take<T>(nodes * width); }
     template <class T>

@@ -59,29 +59,21 @@ int choose_words(int64_t n, int words, int64_t n_sources)
 }
 
 // the workspace: visited | f0 | f1 (uint64[n W] each) | harm (uint64[2 n]; the distance sums only) | control words
-size_t ws_bytes(int64_t n, int W, bool with_harm)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    return 3 * grx_align_up(nn * (size_t)W * 8, 256) + (with_harm ? grx_align_up(nn * 16, 256) : 0) + 256;
-}
-
 struct MsWs {
     uint64_t *visited, *f0, *f1;
     uint64_t *harm;                                          // (lo, hi) per node; null without with_harm
     int32_t *ctrl;
 };
 
-MsWs carve(void *base, int64_t n, int W, bool with_harm)
+MsWs lay_out(GrxCarve &c, int64_t n, int W, bool with_harm)
 {
-    const size_t nn = (size_t)(n > 0 ? n : 1), mask = grx_align_up(nn * (size_t)W * 8, 256);
-    char *p = reinterpret_cast<char *>(base);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
     MsWs ws;
-    ws.visited = reinterpret_cast<uint64_t *>(p); p += mask;
-    ws.f0 = reinterpret_cast<uint64_t *>(p); p += mask;
-    ws.f1 = reinterpret_cast<uint64_t *>(p); p += mask;
-    ws.harm = with_harm ? reinterpret_cast<uint64_t *>(p) : nullptr;
-    if (with_harm) p += grx_align_up(nn * 16, 256);
-    ws.ctrl = reinterpret_cast<int32_t *>(p);
+    ws.visited = c.take<uint64_t>(nn * (size_t)W);
+    ws.f0 = c.take<uint64_t>(nn * (size_t)W);
+    ws.f1 = c.take<uint64_t>(nn * (size_t)W);
+    ws.harm = with_harm ? c.take<uint64_t>(2 * nn) : nullptr;
+    ws.ctrl = c.take<int32_t>(GRX_CTRL_MAX_WORDS);
     return ws;
 }
 
@@ -514,7 +506,7 @@ extern "C" {
 
 size_t grx_distance_sums_workspace_bytes(int64_t n, int words, int64_t n_sources)
 {
-    return ws_bytes(n, choose_words(n, words, n_sources), true);
+    return grx_carve_bytes(lay_out, n, choose_words(n, words, n_sources), true);
 }
 
 int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
@@ -532,10 +524,11 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
     GRX_REQUIRE(lanes_per_row >= 1, "grx_distance_sums: lanes_per_row must be >= 1");
     GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows), "grx_distance_sums: hub list");
     const int W = choose_words(n, words, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, W, true), "grx_distance_sums: workspace %zu bytes, need %zu",
-                workspace_bytes, ws_bytes(n, W, true));
+    GrxCarve c(d_workspace);
+    const MsWs ws = lay_out(c, n, W, true);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_distance_sums: workspace %zu bytes, need %zu", workspace_bytes,
+                c.used);
     hipStream_t st = grx_stream(stream);
-    const MsWs ws = carve(d_workspace, n, W, true);
     const MsArgs a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
                    d_sources, n_sources};
     grx_fill64(reinterpret_cast<uint64_t *>(d_reach), n, 0, st);
@@ -549,7 +542,7 @@ int grx_distance_sums(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col,
 
 size_t grx_eccentricity_workspace_bytes(int64_t n, int words, int64_t n_sources)
 {
-    return ws_bytes(n, choose_words(n, words, n_sources), false);
+    return grx_carve_bytes(lay_out, n, choose_words(n, words, n_sources), false);
 }
 
 int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
@@ -568,10 +561,11 @@ int grx_eccentricity(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
     GRX_REQUIRE(accumulate == 0 || accumulate == 1, "grx_eccentricity: accumulate must be 0 or 1 (got %d)",
                 accumulate);
     const int W = choose_words(n, words, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, W, false), "grx_eccentricity: workspace %zu bytes, need %zu",
-                workspace_bytes, ws_bytes(n, W, false));
+    GrxCarve c(d_workspace);
+    const MsWs ws = lay_out(c, n, W, false);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_eccentricity: workspace %zu bytes, need %zu", workspace_bytes,
+                c.used);
     hipStream_t st = grx_stream(stream);
-    const MsWs ws = carve(d_workspace, n, W, false);
     const MsArgs a{n, d_row_ptr, d_col, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
                    d_sources, n_sources};
     if (!accumulate) {

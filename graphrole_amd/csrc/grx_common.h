@@ -73,6 +73,31 @@ int grx_fetch_begin(void *h_dst_pinned, const void *d_src, size_t bytes, hipStre
 int grx_fetch_wait(hipStream_t st);
 static inline size_t grx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// One walk over a caller-allocated workspace: every array starts on a 256-byte boundary.  base == NULL: only the sizes
+// are wanted and take returns NULL.  `used` ends as the bytes of the workspace.  A file states a layout once, as a
+// function of the carver and the shape; its *_workspace_bytes runs that on a NULL base, its entry point on d_workspace.
+struct GrxCarve {
+    char *base;
+    size_t used = 0;
+    explicit GrxCarve(void *b) : base(reinterpret_cast<char *>(b)) {}
+    template <class T>
+    T *take(size_t count)
+    {
+        T *at = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += grx_align_up(count * sizeof(T), 256);
+        return at;
+    }
+};
+
+// the bytes of the workspace that lay_out(carver, shape...) walks
+template <class LayOut, class... Shape>
+size_t grx_carve_bytes(LayOut lay_out, Shape... shape)
+{
+    GrxCarve c(nullptr);
+    lay_out(c, shape...);
+    return c.used;
+}
+
 // Workgroups of a grid-stride launch: one per `per_block` items, at least 1 and at most `cap`.
 static inline unsigned grx_grid(int64_t items, int64_t per_block, int64_t cap)
 {

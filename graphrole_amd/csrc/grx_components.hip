@@ -71,10 +71,6 @@ enum { PH_TRIM = 0, PH_COLOUR, PH_CLOSE, PH_REMOVE };
 enum { RT_COUNT = GRX_CT_BFS_WORDS, RT_WORDS };
 static_assert(ST_WORDS <= GRX_CTRL_MAX_WORDS && RT_WORDS <= GRX_CTRL_MAX_WORDS, "control words");
 
-size_t array_bytes(int64_t n) { return grx_align_up((size_t)(n > 0 ? n : 1) * sizeof(int32_t), 256); }
-size_t components_ws_bytes(int64_t n) { return 4 * array_bytes(n) + 256; }
-size_t reachable_ws_bytes(int64_t n) { return array_bytes(n) + 256; }
-
 struct CpWs {
     int32_t *gone;                                           // 0 = alive, else the round the node left in
     int32_t *col[2];                                         // the two colour arrays; col[0] holds the size counts afterwards
@@ -82,16 +78,28 @@ struct CpWs {
     int32_t *ctrl;
 };
 
-CpWs carve(void *base, int64_t n)
+CpWs lay_out(GrxCarve &c, int64_t n)
 {
-    char *p = reinterpret_cast<char *>(base);
-    const size_t a = array_bytes(n);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
     CpWs ws;
-    ws.gone = reinterpret_cast<int32_t *>(p); p += a;
-    ws.col[0] = reinterpret_cast<int32_t *>(p); p += a;
-    ws.col[1] = reinterpret_cast<int32_t *>(p); p += a;
-    ws.stamp = reinterpret_cast<int32_t *>(p); p += a;
-    ws.ctrl = reinterpret_cast<int32_t *>(p);
+    ws.gone = c.take<int32_t>(nn);
+    ws.col[0] = c.take<int32_t>(nn);
+    ws.col[1] = c.take<int32_t>(nn);
+    ws.stamp = c.take<int32_t>(nn);
+    ws.ctrl = c.take<int32_t>(GRX_CTRL_MAX_WORDS);
+    return ws;
+}
+
+// of grx_reachable
+struct RcWs {
+    int32_t *level, *ctrl;
+};
+
+RcWs lay_out_reachable(GrxCarve &c, int64_t n)
+{
+    RcWs ws;
+    ws.level = c.take<int32_t>((size_t)(n > 0 ? n : 1));
+    ws.ctrl = c.take<int32_t>(GRX_CTRL_MAX_WORDS);
     return ws;
 }
 
@@ -492,7 +500,7 @@ __global__ __launch_bounds__(CP_BLOCK) void rc_count_kernel(int64_t n, const int
 
 extern "C" {
 
-size_t grx_components_workspace_bytes(int64_t n) { return components_ws_bytes(n); }
+size_t grx_components_workspace_bytes(int64_t n) { return grx_carve_bytes(lay_out, n); }
 
 int grx_components(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                    int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
@@ -519,10 +527,10 @@ int grx_components(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, co
         GRX_REQUIRE(!d_in_row_ptr && !d_in_col && !d_in_hub_rows && n_in_hub_rows == 0 && in_lanes_per_row == 0,
                     "grx_components: GRX_COMPONENTS_CONNECTED takes one symmetric CSR and no in CSR");
     }
-    GRX_REQUIRE(workspace_bytes >= components_ws_bytes(n), "grx_components: workspace %zu bytes, need %zu",
-                workspace_bytes, components_ws_bytes(n));
+    GrxCarve c(d_workspace);
+    const CpWs ws = lay_out(c, n);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_components: workspace %zu bytes, need %zu", workspace_bytes, c.used);
     hipStream_t st = grx_stream(stream);
-    const CpWs ws = carve(d_workspace, n);
     const Csr out = {d_row_ptr, d_col, (int64_t)GRX_HUB_FACTOR * lanes_per_row};
     const unsigned ngrid = grx_grid(n, CP_BLOCK, CP_MAX_BLOCKS);
     const unsigned rgrid = grx_grid(n, CP_BLOCK / CP_GROUP, CP_MAX_ROW_BLOCKS);
@@ -582,7 +590,7 @@ int grx_components(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, co
     return GRX_OK;
 }
 
-size_t grx_reachable_workspace_bytes(int64_t n) { return reachable_ws_bytes(n); }
+size_t grx_reachable_workspace_bytes(int64_t n) { return grx_carve_bytes(lay_out_reachable, n); }
 
 int grx_reachable(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                   int64_t n_hub_rows, int lanes_per_row, int32_t *d_flag, int64_t *h_count, int64_t *h_levels,
@@ -595,11 +603,11 @@ int grx_reachable(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, con
     GRX_REQUIRE(d_row_ptr && d_col && d_flag && d_workspace, "grx_reachable: null pointer");
     GRX_REQUIRE(lanes_per_row >= 1, "grx_reachable: lanes_per_row must be >= 1");
     GRX_REQUIRE(n_hub_rows >= 0 && n_hub_rows <= n && (n_hub_rows == 0 || d_hub_rows), "grx_reachable: hub list");
-    GRX_REQUIRE(workspace_bytes >= reachable_ws_bytes(n), "grx_reachable: workspace %zu bytes, need %zu",
-                workspace_bytes, reachable_ws_bytes(n));
+    GrxCarve c(d_workspace);
+    const RcWs ws = lay_out_reachable(c, n);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_reachable: workspace %zu bytes, need %zu", workspace_bytes, c.used);
     hipStream_t st = grx_stream(stream);
-    int32_t *level = reinterpret_cast<int32_t *>(d_workspace);
-    int32_t *ctrl = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d_workspace) + array_bytes(n));
+    int32_t *level = ws.level, *ctrl = ws.ctrl;
     const Csr g = {d_row_ptr, d_col, (int64_t)GRX_HUB_FACTOR * lanes_per_row};
     const unsigned ngrid = grx_grid(n, CP_BLOCK, CP_MAX_BLOCKS);
     const unsigned rgrid = grx_grid(n, CP_BLOCK / CP_GROUP, CP_MAX_ROW_BLOCKS);

@@ -14,6 +14,8 @@
 // All results are integers (and copied weights): bit-identical to the host construction (tests compare them).
 #include "grx_common.h"
 
+#include <algorithm>
+
 namespace {
 
 constexpr uint64_t ING_SENTINEL = ~0ull;
@@ -305,31 +307,46 @@ __global__ __launch_bounds__(256) void permute_columns_kernel(int64_t n, GrxPtrT
 }
 
 struct IngestPlan {
-    size_t off_deg, off_deg_in, off_keys_n, off_sorted_n, off_cnt, off_cnt_in, off_tsum, off_key_a, off_key_b, off_out, off_sort,
-        total;
+    int32_t *deg, *deg_in;
+    uint64_t *keys_n, *sorted_n;
+    int64_t *cnt, *cnt_in, *tsum;
+    uint64_t *key_a, *key_b, *out;
+    char *sort_ws;                                           // of grx_internal_sort_u64, n or `slots` keys
     int64_t slots;
 };
 
-IngestPlan ingest_plan(int64_t n, int64_t m, int directed)
+// n, m >= 1 (both callers see to it), so no array is empty
+IngestPlan ingest_plan(GrxCarve &c, int64_t n, int64_t m, int directed)
 {
     IngestPlan p;
     p.slots = directed ? m : 2 * m;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += grx_align_up(bytes ? bytes : 8, 256); return at; };
-    p.off_deg = take((size_t)n * 4);
-    p.off_deg_in = take((size_t)n * 4);
-    p.off_keys_n = take((size_t)n * 8);
-    p.off_sorted_n = take((size_t)n * 8);
-    p.off_cnt = take((size_t)(n + 1) * 8);
-    p.off_cnt_in = take((size_t)(n + 1) * 8);
-    p.off_tsum = take((size_t)(grx_ceil_div(n > 1 ? n : 1, ING_SCAN_TILE) + 1) * 8);
-    p.off_key_a = take((size_t)p.slots * 8);
-    p.off_key_b = take((size_t)p.slots * 8);
-    p.off_out = take((size_t)p.slots * 8);
-    const size_t s1 = grx_sort_workspace_bytes(n > 1 ? n : 1, 1), s2 = grx_sort_workspace_bytes(p.slots > 1 ? p.slots : 1, 1);
-    p.off_sort = take(s1 > s2 ? s1 : s2);
-    p.total = o;
+    p.deg = c.take<int32_t>(n);
+    p.deg_in = c.take<int32_t>(n);
+    p.keys_n = c.take<uint64_t>(n);
+    p.sorted_n = c.take<uint64_t>(n);
+    p.cnt = c.take<int64_t>(n + 1);
+    p.cnt_in = c.take<int64_t>(n + 1);
+    p.tsum = c.take<int64_t>(grx_ceil_div(n, ING_SCAN_TILE) + 1);
+    p.key_a = c.take<uint64_t>(p.slots);
+    p.key_b = c.take<uint64_t>(p.slots);
+    p.out = c.take<uint64_t>(p.slots);
+    p.sort_ws = c.take<char>(std::max(grx_sort_workspace_bytes(n, 1), grx_sort_workspace_bytes(p.slots, 1)));
     return p;
+}
+
+struct OrientWs {
+    int32_t *dprime;                                         // grx_orient_count leaves it for grx_orient_fill
+    int64_t *cnt, *tsum;
+};
+
+OrientWs orient_lay_out(GrxCarve &c, int64_t n)
+{
+    if (n < 1) n = 1;
+    OrientWs w;
+    w.dprime = c.take<int32_t>(n);
+    w.cnt = c.take<int64_t>(n + 1);
+    w.tsum = c.take<int64_t>(grx_ceil_div(n, ING_SCAN_TILE) + 1);
+    return w;
 }
 
 }  // namespace
@@ -338,7 +355,7 @@ extern "C" {
 
 size_t grx_ingest_workspace_bytes(int64_t n, int64_t m, int directed)
 {
-    return ingest_plan(n < 1 ? 1 : n, m < 1 ? 1 : m, directed).total;
+    return grx_carve_bytes(ingest_plan, n < 1 ? 1 : n, m < 1 ? 1 : m, directed);
 }
 
 int grx_ingest(int64_t n, int64_t m, const int32_t *d_src, const int32_t *d_dst, const double *d_w, int directed,
@@ -351,61 +368,50 @@ int grx_ingest(int64_t n, int64_t m, const int32_t *d_src, const int32_t *d_dst,
     GRX_REQUIRE(!d_w || d_wcol, "grx_ingest: weights need an output array");
     GRX_REQUIRE(!directed || (d_t_row_ptr && d_t_col && (!d_w || d_t_w)), "grx_ingest: directed graphs need the transposed outputs");
     GRX_REQUIRE(nnz >= 1 && nnz <= (directed ? m : 2 * m), "grx_ingest: nnz outside (0, %s]", directed ? "m" : "2m");
-    const IngestPlan p = ingest_plan(n, m, directed);
-    if (workspace_bytes < p.total) {
-        grx_set_error("grx_ingest: workspace %zu < %zu", workspace_bytes, p.total);
+    GrxCarve c(d_workspace);
+    const IngestPlan p = ingest_plan(c, n, m, directed);
+    if (workspace_bytes < c.used) {
+        grx_set_error("grx_ingest: workspace %zu < %zu", workspace_bytes, c.used);
         return GRX_ERR_WORKSPACE;
     }
     hipStream_t st = grx_stream(stream);
-    char *ws = reinterpret_cast<char *>(d_workspace);
-    int32_t *deg = reinterpret_cast<int32_t *>(ws + p.off_deg);
-    int32_t *deg_in = reinterpret_cast<int32_t *>(ws + p.off_deg_in);
-    uint64_t *keys_n = reinterpret_cast<uint64_t *>(ws + p.off_keys_n);
-    uint64_t *sorted_n = reinterpret_cast<uint64_t *>(ws + p.off_sorted_n);
-    int64_t *cnt = reinterpret_cast<int64_t *>(ws + p.off_cnt);
-    int64_t *cnt_in = reinterpret_cast<int64_t *>(ws + p.off_cnt_in);
-    int64_t *tsum = reinterpret_cast<int64_t *>(ws + p.off_tsum);
-    uint64_t *key_a = reinterpret_cast<uint64_t *>(ws + p.off_key_a);
-    uint64_t *key_b = reinterpret_cast<uint64_t *>(ws + p.off_key_b);
-    void *sort_ws = ws + p.off_sort;
     const int egrid = (int)(grx_ceil_div(m, 256) > 4096 ? 4096 : grx_ceil_div(m, 256));
     const int ngrid = (int)grx_ceil_div(n, 256);
-    GRX_CHECK_HIP(hipMemsetAsync(deg, 0, (size_t)n * 4, st));
-    GRX_CHECK_HIP(hipMemsetAsync(deg_in, 0, (size_t)n * 4, st));
-    ing_degree_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, directed, deg, deg_in);
-    ing_node_keys_kernel<<<ngrid, 256, 0, st>>>(n, deg, keys_n);
+    GRX_CHECK_HIP(hipMemsetAsync(p.deg, 0, (size_t)n * 4, st));
+    GRX_CHECK_HIP(hipMemsetAsync(p.deg_in, 0, (size_t)n * 4, st));
+    ing_degree_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, directed, p.deg, p.deg_in);
+    ing_node_keys_kernel<<<ngrid, 256, 0, st>>>(n, p.deg, p.keys_n);
     GRX_LAUNCH_CHECK();
-    int rc = grx_internal_sort_u64(n, keys_n, sorted_n, sort_ws, st);
+    int rc = grx_internal_sort_u64(n, p.keys_n, p.sorted_n, p.sort_ws, st);
     if (rc != GRX_OK) return rc;
-    ing_perm_kernel<<<ngrid, 256, 0, st>>>(n, sorted_n, deg, deg_in, d_perm, d_inv, cnt, directed ? cnt_in : nullptr);
+    ing_perm_kernel<<<ngrid, 256, 0, st>>>(n, p.sorted_n, p.deg, p.deg_in, d_perm, d_inv, p.cnt, directed ? p.cnt_in : nullptr);
     GRX_LAUNCH_CHECK();
-    rc = ing_scan(n, cnt, d_row_ptr, tsum, st);
+    rc = ing_scan(n, p.cnt, d_row_ptr, p.tsum, st);
     if (rc != GRX_OK) return rc;
     if (directed) {
-        rc = ing_scan(n, cnt_in, d_t_row_ptr, tsum, st);
+        rc = ing_scan(n, p.cnt_in, d_t_row_ptr, p.tsum, st);
         if (rc != GRX_OK) return rc;
     }
     const int agrid = (int)grx_ceil_div(nnz, 256);
     // adjacency order, then ascending columns, of the out-adjacency
-    ing_arc_keys_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, d_inv, directed ? 1 : 0, key_a, key_b);
+    ing_arc_keys_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, d_inv, directed ? 1 : 0, p.key_a, p.key_b);
     GRX_LAUNCH_CHECK();
-    uint64_t *out = reinterpret_cast<uint64_t *>(ws + p.off_out);
-    rc = grx_internal_sort_u64(p.slots, key_a, out, sort_ws, st);          // sentinels (second arc of a loop) sort last
+    rc = grx_internal_sort_u64(p.slots, p.key_a, p.out, p.sort_ws, st);  // sentinels (second arc of a loop) sort last
     if (rc != GRX_OK) return rc;
-    ing_adj_cols_kernel<<<agrid, 256, 0, st>>>(nnz, out, d_src, d_dst, d_inv, directed ? 0 : 1, d_agg_col);
+    ing_adj_cols_kernel<<<agrid, 256, 0, st>>>(nnz, p.out, d_src, d_dst, d_inv, directed ? 0 : 1, d_agg_col);
     GRX_LAUNCH_CHECK();
-    rc = grx_internal_sort_u64(p.slots, key_b, out, sort_ws, st);
+    rc = grx_internal_sort_u64(p.slots, p.key_b, p.out, p.sort_ws, st);
     if (rc != GRX_OK) return rc;
-    ing_low32_kernel<<<agrid, 256, 0, st>>>(nnz, out, d_col);
+    ing_low32_kernel<<<agrid, 256, 0, st>>>(nnz, p.out, d_col);
     if (d_w) ing_weights_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, d_w, d_inv, directed ? 1 : 0, d_row_ptr, d_col, d_wcol);
     GRX_LAUNCH_CHECK();
     if (directed) {
         // the transposed (in-) adjacency: rows = targets, columns = sources, ascending
-        ing_arc_keys_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, d_inv, 2, nullptr, key_b);
+        ing_arc_keys_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, d_inv, 2, nullptr, p.key_b);
         GRX_LAUNCH_CHECK();
-        rc = grx_internal_sort_u64(m, key_b, out, sort_ws, st);
+        rc = grx_internal_sort_u64(m, p.key_b, p.out, p.sort_ws, st);
         if (rc != GRX_OK) return rc;
-        ing_low32_kernel<<<(int)grx_ceil_div(m, 256), 256, 0, st>>>(m, out, d_t_col);
+        ing_low32_kernel<<<(int)grx_ceil_div(m, 256), 256, 0, st>>>(m, p.out, d_t_col);
         if (d_w) ing_weights_kernel<<<egrid, 256, 0, st>>>(m, d_src, d_dst, d_w, d_inv, 2, d_t_row_ptr, d_t_col, d_t_w);
         GRX_LAUNCH_CHECK();
     }
@@ -430,35 +436,28 @@ int grx_permute_columns(int64_t n, int F, const double *const *h_col_ptrs, const
     return GRX_OK;
 }
 
-size_t grx_orient_workspace_bytes(int64_t n)
-{
-    if (n < 1) n = 1;
-    return grx_align_up((size_t)n * 4, 256) + grx_align_up((size_t)(n + 1) * 8, 256) +
-           grx_align_up((size_t)(grx_ceil_div(n, ING_SCAN_TILE) + 1) * 8, 256);
-}
+size_t grx_orient_workspace_bytes(int64_t n) { return grx_carve_bytes(orient_lay_out, n); }
 
 int grx_orient_count(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, int64_t *d_o_row_ptr, void *d_workspace,
                      size_t workspace_bytes, void *stream)
 {
     GRX_REQUIRE(n >= 1 && d_row_ptr && d_col && d_o_row_ptr && d_workspace, "grx_orient_count: bad arguments");
-    if (workspace_bytes < grx_orient_workspace_bytes(n)) {
+    GrxCarve c(d_workspace);
+    const OrientWs w = orient_lay_out(c, n);
+    if (workspace_bytes < c.used) {
         grx_set_error("grx_orient_count: workspace too small");
         return GRX_ERR_WORKSPACE;
     }
     hipStream_t st = grx_stream(stream);
-    char *ws = reinterpret_cast<char *>(d_workspace);
-    int32_t *dprime = reinterpret_cast<int32_t *>(ws);
-    int64_t *cnt = reinterpret_cast<int64_t *>(ws + grx_align_up((size_t)n * 4, 256));
-    int64_t *tsum = reinterpret_cast<int64_t *>(ws + grx_align_up((size_t)n * 4, 256) + grx_align_up((size_t)(n + 1) * 8, 256));
     const int ngrid = (int)grx_ceil_div(n, 256);
-    orient_dprime_kernel<<<ngrid, 256, 0, st>>>(n, d_row_ptr, d_col, dprime);
+    orient_dprime_kernel<<<ngrid, 256, 0, st>>>(n, d_row_ptr, d_col, w.dprime);
     {
         const int64_t want = grx_ceil_div(n, 4);                         // a wavefront per row, four per workgroup
         const int wgrid = (int)(want > GRX_NUM_CU * 32 ? GRX_NUM_CU * 32 : want);
-        orient_count_kernel<<<wgrid, 256, 0, st>>>(n, d_row_ptr, d_col, dprime, cnt);
+        orient_count_kernel<<<wgrid, 256, 0, st>>>(n, d_row_ptr, d_col, w.dprime, w.cnt);
     }
     GRX_LAUNCH_CHECK();
-    return ing_scan(n, cnt, d_o_row_ptr, tsum, st);
+    return ing_scan(n, w.cnt, d_o_row_ptr, w.tsum, st);
 }
 
 int grx_orient_fill(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int64_t *d_o_row_ptr, int64_t o_nnz,
@@ -466,12 +465,13 @@ int grx_orient_fill(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, c
 {
     GRX_REQUIRE(n >= 1 && d_row_ptr && d_col && d_o_row_ptr && d_workspace && o_nnz >= 0, "grx_orient_fill: bad arguments");
     GRX_REQUIRE(o_nnz == 0 || (d_o_col && d_o_arc), "grx_orient_fill: NULL output");
-    if (workspace_bytes < grx_orient_workspace_bytes(n)) {
+    GrxCarve c(d_workspace);
+    const int32_t *dprime = orient_lay_out(c, n).dprime;                        // left there by grx_orient_count
+    if (workspace_bytes < c.used) {
         grx_set_error("grx_orient_fill: workspace too small");
         return GRX_ERR_WORKSPACE;
     }
     hipStream_t st = grx_stream(stream);
-    const int32_t *dprime = reinterpret_cast<const int32_t *>(d_workspace);      // left there by grx_orient_count
     const int64_t want = grx_ceil_div(n, 4);
     const int wgrid = (int)(want > GRX_NUM_CU * 32 ? GRX_NUM_CU * 32 : want);
     orient_fill_kernel<<<wgrid, 256, 0, st>>>(n, d_row_ptr, d_col, dprime, d_o_row_ptr, d_o_col);

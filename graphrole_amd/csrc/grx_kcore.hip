@@ -47,12 +47,6 @@ constexpr int KC_ROUND_BATCH = 16;                           // rounds enqueued 
 constexpr int KC_MAX_BLOCKS = 2048;                          // workgroups of kc_init and kc_peel
 constexpr int KC_OUT_HUB = 1, KC_IN_HUB = 2;
 
-size_t ws_bytes(int64_t n)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    return 4 * grx_align_up(nn * 4, 256) + 256;
-}
-
 // the workspace, the outputs, and the items of grx_peel.h: a node, alive while its state word is <= 0, valued by deg
 struct KcState {
     int32_t *deg, *state;
@@ -68,16 +62,15 @@ struct KcState {
     }
 };
 
-KcState carve(void *base, int64_t n, int64_t *core, int64_t *onion)
+KcState lay_out(GrxCarve &c, int64_t n, int64_t *core, int64_t *onion)
 {
-    const size_t nn = (size_t)(n > 0 ? n : 1), step = grx_align_up(nn * 4, 256);
-    char *p = reinterpret_cast<char *>(base);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
     KcState s;
-    s.deg = reinterpret_cast<int32_t *>(p); p += step;
-    s.state = reinterpret_cast<int32_t *>(p); p += step;
-    s.pl.list0 = reinterpret_cast<int32_t *>(p); p += step;
-    s.pl.list1 = reinterpret_cast<int32_t *>(p); p += step;
-    s.pl.ctrl = reinterpret_cast<int32_t *>(p);
+    s.deg = c.take<int32_t>(nn);
+    s.state = c.take<int32_t>(nn);
+    s.pl.list0 = c.take<int32_t>(nn);
+    s.pl.list1 = c.take<int32_t>(nn);
+    s.pl.ctrl = c.take<int32_t>(GRX_CTRL_MAX_WORDS);
     s.core = core;
     s.onion = onion;
     return s;
@@ -190,7 +183,7 @@ __global__ __launch_bounds__(KC_BLOCK) void kc_hub_kernel(int64_t n, const int64
 
 extern "C" {
 
-size_t grx_core_numbers_workspace_bytes(int64_t n) { return ws_bytes(n); }
+size_t grx_core_numbers_workspace_bytes(int64_t n) { return grx_carve_bytes(lay_out, n, nullptr, nullptr); }
 
 int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const int32_t *d_hub_rows,
                      int64_t n_hub_rows, int lanes_per_row, const int64_t *d_in_row_ptr, const int32_t *d_in_col,
@@ -211,10 +204,10 @@ int grx_core_numbers(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, 
         GRX_REQUIRE(!d_in_col && !d_in_hub_rows && n_in_hub_rows == 0 && in_lanes_per_row == 0,
                     "grx_core_numbers: the in CSR must be given whole or not at all");
     }
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n), "grx_core_numbers: workspace %zu bytes, need %zu", workspace_bytes,
-                ws_bytes(n));
+    GrxCarve c(d_workspace);
+    const KcState s = lay_out(c, n, d_core, d_onion);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_core_numbers: workspace %zu bytes, need %zu", workspace_bytes, c.used);
     hipStream_t st = grx_stream(stream);
-    const KcState s = carve(d_workspace, n, d_core, d_onion);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
     const int64_t in_hub_degree = (int64_t)GRX_HUB_FACTOR * in_lanes_per_row;
     const unsigned init_grid = grx_grid(n, KC_BLOCK, KC_MAX_BLOCKS);

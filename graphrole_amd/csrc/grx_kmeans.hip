@@ -1867,12 +1867,17 @@ struct KmPlan {
     int64_t ntiles;
     int nb;                                                    // workgroups of the strided reductions
     int block_shift, nblocks;                                  // index blocks of the cumulative sum
-    size_t off_state, off_x, off_ds, off_bacc, off_tsum, off_part, off_seedx, off_seedid, off_sorted, off_uniform,
-        off_xs, off_perm, off_rank, off_sb, off_top, off_top2, off_P, off_lloyd, off_sort, total;
     size_t sorted_ld;
+    KmState *state;
+    double *x, *ds, *tsum, *part, *seeds_x, *sorted2, *uniform, *xs, *xtop, *xtop2, *P, *lloyd;
+    i64 *bacc;
+    int64_t *seeds_id;
+    uint32_t *perm, *rank;
+    KmSorted *sb;
+    char *sort_ws;                                             // of grx_internal_sort_pairs, m values
 };
 
-KmPlan km_plan(int64_t m, int k)
+KmPlan km_plan(GrxCarve &c, int64_t m, int k)
 {
     KmPlan p;
     p.ntiles = grx_ceil_div(m, KM_TILE);
@@ -1882,28 +1887,25 @@ KmPlan km_plan(int64_t m, int k)
     while (grx_ceil_div(m, (int64_t)1 << p.block_shift) > KM_MAX_BLOCKS) ++p.block_shift;
     p.nblocks = (int)grx_ceil_div(m, (int64_t)1 << p.block_shift);
     p.sorted_ld = grx_align_up((size_t)(k + 1) * 8, 256) / 8;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += grx_align_up(bytes, 256); return at; };
-    p.off_state = take(sizeof(KmState));
-    p.off_x = take((size_t)m * 8);
-    p.off_ds = take((size_t)m * 8);
-    p.off_bacc = take((size_t)(KM_MAX_BLOCKS + 32) * 32);
-    p.off_tsum = take((size_t)p.ntiles * 8);
-    p.off_part = take((size_t)3 * p.nb * 8);
-    p.off_seedx = take((size_t)k * 8);
-    p.off_seedid = take((size_t)k * 8);
-    p.off_sorted = take(2 * p.sorted_ld * 8);
-    p.off_uniform = take((size_t)(k > 1 ? k - 1 : 1) * KM_MAX_TRIALS * 8);
-    p.off_xs = take((size_t)m * 8);
-    p.off_perm = take((size_t)m * 4);
-    p.off_rank = take((size_t)m * 4);
-    p.off_sb = take((size_t)grx_ceil_div(m, KM_CHUNK) * sizeof(KmSorted));
-    p.off_top = take((size_t)grx_ceil_div(m, KM_CHUNK) * 8);
-    p.off_top2 = take((size_t)KM_TOP2 * 8);
-    p.off_P = take((size_t)(m + 1) * 8);
-    p.off_lloyd = take((size_t)k * 8 * 16);
-    p.off_sort = take(grx_internal_sort_pairs_workspace_bytes(m));
-    p.total = o;
+    p.state = c.take<KmState>(1);
+    p.x = c.take<double>(m);
+    p.ds = c.take<double>(m);
+    p.bacc = c.take<i64>((size_t)(KM_MAX_BLOCKS + 32) * 4);   // 32 bytes per entry
+    p.tsum = c.take<double>(p.ntiles);
+    p.part = c.take<double>((size_t)3 * p.nb);
+    p.seeds_x = c.take<double>(k);
+    p.seeds_id = c.take<int64_t>(k);
+    p.sorted2 = c.take<double>(2 * p.sorted_ld);
+    p.uniform = c.take<double>((size_t)(k > 1 ? k - 1 : 1) * KM_MAX_TRIALS);
+    p.xs = c.take<double>(m);
+    p.perm = c.take<uint32_t>(m);
+    p.rank = c.take<uint32_t>(m);
+    p.sb = c.take<KmSorted>(grx_ceil_div(m, KM_CHUNK));
+    p.xtop = c.take<double>(grx_ceil_div(m, KM_CHUNK));
+    p.xtop2 = c.take<double>(KM_TOP2);
+    p.P = c.take<double>(m + 1);
+    p.lloyd = c.take<double>((size_t)k * 16);
+    p.sort_ws = c.take<char>(grx_internal_sort_pairs_workspace_bytes(m));
     return p;
 }
 
@@ -1932,7 +1934,7 @@ size_t grx_kmeans1d_workspace_bytes(int64_t m, int k)
 {
     if (m < 1) m = 1;
     if (k < 1) k = 1;
-    return km_plan(m, k).total;
+    return grx_carve_bytes(km_plan, m, k);
 }
 
 int grx_kmeans1d(int64_t m, const double *d_values, int k, int64_t first_seed, const double *h_uniform, int n_trials,
@@ -1950,43 +1952,28 @@ int grx_kmeans1d(int64_t m, const double *d_values, int k, int64_t first_seed, c
     GRX_REQUIRE(n_trials >= 1 && n_trials <= KM_MAX_TRIALS, "grx_kmeans1d: n_trials outside [1, %d]", KM_MAX_TRIALS);
     GRX_REQUIRE(d_values && d_quantized && d_centers && d_info && d_workspace && (k == 1 || h_uniform),
                 "grx_kmeans1d: NULL pointer");
-    const KmPlan p = km_plan(m, k);
-    if (workspace_bytes < p.total) {
-        grx_set_error("grx_kmeans1d: workspace %zu < %zu", workspace_bytes, p.total);
+    GrxCarve c(d_workspace);
+    const KmPlan p = km_plan(c, m, k);
+    if (workspace_bytes < c.used) {
+        grx_set_error("grx_kmeans1d: workspace %zu < %zu", workspace_bytes, c.used);
         return GRX_ERR_WORKSPACE;
     }
     hipStream_t st = grx_stream(stream);
-    char *ws = reinterpret_cast<char *>(d_workspace);
-    KmState *state = reinterpret_cast<KmState *>(ws + p.off_state);
-    double *x = reinterpret_cast<double *>(ws + p.off_x);
-    double *ds = reinterpret_cast<double *>(ws + p.off_ds);
-    i64 *bacc = reinterpret_cast<i64 *>(ws + p.off_bacc);
-    double *tsum = reinterpret_cast<double *>(ws + p.off_tsum);
-    double *part = reinterpret_cast<double *>(ws + p.off_part);
-    double *seeds_x = reinterpret_cast<double *>(ws + p.off_seedx);
-    int64_t *seeds_id = reinterpret_cast<int64_t *>(ws + p.off_seedid);
-    double *sorted2 = reinterpret_cast<double *>(ws + p.off_sorted);
-    double *d_uniform = reinterpret_cast<double *>(ws + p.off_uniform);
-    double *xs = reinterpret_cast<double *>(ws + p.off_xs);
-    uint32_t *perm = reinterpret_cast<uint32_t *>(ws + p.off_perm);
-    uint32_t *rank = reinterpret_cast<uint32_t *>(ws + p.off_rank);
-    KmSorted *sb = reinterpret_cast<KmSorted *>(ws + p.off_sb);
-    double *P = reinterpret_cast<double *>(ws + p.off_P);
     GRX_PROF(GRX_K_QUANT, st);
     if (k > 1)
-        GRX_CHECK_HIP(hipMemcpyAsync(d_uniform, h_uniform, (size_t)(k - 1) * n_trials * 8, hipMemcpyHostToDevice, st));
-    GRX_CHECK_HIP(hipMemsetAsync(bacc, 0, (size_t)(KM_MAX_BLOCKS + 32) * 32, st));
+        GRX_CHECK_HIP(hipMemcpyAsync(p.uniform, h_uniform, (size_t)(k - 1) * n_trials * 8, hipMemcpyHostToDevice, st));
+    GRX_CHECK_HIP(hipMemsetAsync(p.bacc, 0, (size_t)(KM_MAX_BLOCKS + 32) * 32, st));
     // mean and tolerance (KMeans.fit: X -= X.mean(axis=0); tol = mean(var(X, axis=0)) * 1e-4)
-    km_sum_kernel<<<p.nb, 256, 0, st>>>(d_values, m, state, 0, part);
-    km_moment_final_kernel<<<1, 256, 0, st>>>(part, p.nb, m, 0, rel_tol, d_values, first_seed, state);
-    km_sum_kernel<<<p.nb, 256, 0, st>>>(d_values, m, state, 1, part);
-    km_moment_final_kernel<<<1, 256, 0, st>>>(part, p.nb, m, 1, rel_tol, d_values, first_seed, state);
+    km_sum_kernel<<<p.nb, 256, 0, st>>>(d_values, m, p.state, 0, p.part);
+    km_moment_final_kernel<<<1, 256, 0, st>>>(p.part, p.nb, m, 0, rel_tol, d_values, first_seed, p.state);
+    km_sum_kernel<<<p.nb, 256, 0, st>>>(d_values, m, p.state, 1, p.part);
+    km_moment_final_kernel<<<1, 256, 0, st>>>(p.part, p.nb, m, 1, rel_tol, d_values, first_seed, p.state);
     // (the sorted list of seeds with n entries lives in buffer n & 1: the first seed goes to buffer 1)
-    km_init_kernel<<<(int)p.ntiles, 256, 0, st>>>(d_values, m, first_seed, state, x, bacc, p.block_shift, seeds_x, seeds_id,
-                                                  sorted2 + p.sorted_ld);
+    km_init_kernel<<<(int)p.ntiles, 256, 0, st>>>(d_values, m, first_seed, p.state, p.x, p.bacc, p.block_shift, p.seeds_x, p.seeds_id,
+                                                  p.sorted2 + p.sorted_ld);
     GRX_LAUNCH_CHECK();
     // the values in ascending order with the index each came from (the Lloyd iterations need the order as well)
-    int rc = grx_internal_sort_pairs(m, x, xs, perm, ws + p.off_sort, st);
+    int rc = grx_internal_sort_pairs(m, p.x, p.xs, p.perm, p.sort_ws, st);
     if (rc != GRX_OK) return rc;
     const int64_t want = grx_ceil_div(m, 256 * 4);
     const int stream_grid = (int)(want > 2048 ? 2048 : want);
@@ -2003,16 +1990,16 @@ int grx_kmeans1d(int64_t m, const double *d_values, int k, int64_t first_seed, c
         const int vpt = m <= 1024 ? 1 : KM_SMALL_M / 1024;
         const int threads = (int)grx_align_up((size_t)grx_ceil_div(m, vpt), 64);
         if (vpt == 1 && n_trials <= 8)
-            km_seed_small_kernel<1, 8><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, d_uniform, n_trials, k, state, seeds_x, seeds_id);
+            km_seed_small_kernel<1, 8><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, p.uniform, n_trials, k, p.state, p.seeds_x, p.seeds_id);
         else if (vpt == 1)
-            km_seed_small_kernel<1, KM_MAX_TRIALS><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, d_uniform, n_trials, k, state,
-                                                                          seeds_x, seeds_id);
+            km_seed_small_kernel<1, KM_MAX_TRIALS><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, p.uniform, n_trials, k, p.state,
+                                                                          p.seeds_x, p.seeds_id);
         else if (n_trials <= 8)
-            km_seed_small_kernel<KM_SMALL_M / 1024, 8><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, d_uniform, n_trials, k, state,
-                                                                              seeds_x, seeds_id);
+            km_seed_small_kernel<KM_SMALL_M / 1024, 8><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, p.uniform, n_trials, k, p.state,
+                                                                              p.seeds_x, p.seeds_id);
         else
-            km_seed_small_kernel<KM_SMALL_M / 1024, KM_MAX_TRIALS><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, d_uniform, n_trials,
-                                                                                          k, state, seeds_x, seeds_id);
+            km_seed_small_kernel<KM_SMALL_M / 1024, KM_MAX_TRIALS><<<1, threads, 0, st>>>(d_values, (int)m, first_seed, p.uniform, n_trials,
+                                                                                          k, p.state, p.seeds_x, p.seeds_id);
     } else if (k > 1) {
         // GRX_KMEANS_GAIN_PASS=1 (and the full ranges): every candidate's gain by a pass over its range in exact integer
         // arithmetic (km_gain_kernel) instead of the closed form over sorted blocks inside the pick (km_pick_tail, D):
@@ -2024,12 +2011,12 @@ int grx_kmeans1d(int64_t m, const double *d_values, int k, int64_t first_seed, c
         static const int slow_pick = [] { const char *e = std::getenv("GRX_KMEANS_SLOW_PICK"); return (e && *e == '1') ? 1 : 0; }();
         const int64_t max_chunks = grx_ceil_div(m, KM_CHUNK);
         KmTop top;
-        top.xtop = reinterpret_cast<double *>(ws + p.off_top);
-        top.xtop2 = reinterpret_cast<double *>(ws + p.off_top2);
+        top.xtop = p.xtop;
+        top.xtop2 = p.xtop2;
         top.nsb = max_chunks;
         top.s2 = (int)grx_ceil_div(max_chunks, KM_TOP2);
         top.n2 = (int)grx_ceil_div(max_chunks, top.s2);
-        km_sorted_init_kernel<<<(int)max_chunks, 256, 0, st>>>(xs, perm, m, state, ds, rank, sb, top);
+        km_sorted_init_kernel<<<(int)max_chunks, 256, 0, st>>>(p.xs, p.perm, m, p.state, p.ds, p.rank, p.sb, top);
         l_xtop = top.xtop; l_xtop2 = top.xtop2; l_nsb = top.nsb; l_n2 = top.n2; l_s2 = top.s2;
         const int range_grid = (int)(max_chunks < KM_RANGE_GRID ? max_chunks : KM_RANGE_GRID);
         static const int update_grid_max = [] { const char *e = std::getenv("GRX_KMEANS_UPDATE_GRID"); return e ? atoi(e) : KM_UPDATE_GRID; }();
@@ -2044,36 +2031,36 @@ int grx_kmeans1d(int64_t m, const double *d_values, int k, int64_t first_seed, c
         static const int lose_at = [] { const char *e = std::getenv("GRX_KMEANS_LOSE_A_SUM"); return e ? atoi(e) : -1; }();
         for (int c = 1; c < k; ++c) {
             const int merge = (closed && c < k - 1 && (double)c >= merge_from) ? 1 : 0;
-            km_prep_kernel<<<dim3(KM_SUB, n_trials), 256, 0, st>>>(xs, ds, rank, perm, m, bacc, p.nblocks, p.block_shift,
-                                                                   d_uniform + (size_t)(c - 1) * n_trials, n_trials, c, c >= 2, 1,
-                                                                   full_range, closed, slow_pick, merge, c == lose_at ? 1 : 0, sb, top,
-                                                                   state, seeds_x, seeds_id, sorted2, (int)p.sorted_ld);
+            km_prep_kernel<<<dim3(KM_SUB, n_trials), 256, 0, st>>>(p.xs, p.ds, p.rank, p.perm, m, p.bacc, p.nblocks, p.block_shift,
+                                                                   p.uniform + (size_t)(c - 1) * n_trials, n_trials, c, c >= 2, 1,
+                                                                   full_range, closed, slow_pick, merge, c == lose_at ? 1 : 0, p.sb, top,
+                                                                   p.state, p.seeds_x, p.seeds_id, p.sorted2, (int)p.sorted_ld);
             if (!closed) {
-                if (n_trials <= 8) km_gain_kernel<8><<<range_grid, 256, 0, st>>>(xs, ds, state, c, n_trials);
-                else km_gain_kernel<KM_MAX_TRIALS><<<range_grid, 256, 0, st>>>(xs, ds, state, c, n_trials);
+                if (n_trials <= 8) km_gain_kernel<8><<<range_grid, 256, 0, st>>>(p.xs, p.ds, p.state, c, n_trials);
+                else km_gain_kernel<KM_MAX_TRIALS><<<range_grid, 256, 0, st>>>(p.xs, p.ds, p.state, c, n_trials);
             }
             if (c < k - 1 && !merge)                               // the distances to the last seed are never needed
-                km_update_kernel<<<update_grid, KM_UPDATE_THREADS, 0, st>>>(xs, ds, perm, bacc, p.nblocks, p.block_shift, m, sb, state,
+                km_update_kernel<<<update_grid, KM_UPDATE_THREADS, 0, st>>>(p.xs, p.ds, p.perm, p.bacc, p.nblocks, p.block_shift, m, p.sb, p.state,
                                                                             c, n_trials, closed);
         }
-        km_prep_kernel<<<dim3(1, 1), 256, 0, st>>>(xs, ds, rank, perm, m, bacc, p.nblocks, p.block_shift, d_uniform, n_trials, k, 1,
-                                                   0, full_range, closed, slow_pick, 0, 0, sb, top, state, seeds_x, seeds_id, sorted2,
+        km_prep_kernel<<<dim3(1, 1), 256, 0, st>>>(p.xs, p.ds, p.rank, p.perm, m, p.bacc, p.nblocks, p.block_shift, p.uniform, n_trials, k, 1,
+                                                   0, full_range, closed, slow_pick, 0, 0, p.sb, top, p.state, p.seeds_x, p.seeds_id, p.sorted2,
                                                    (int)p.sorted_ld);
     }
     GRX_LAUNCH_CHECK();
     // Lloyd on the sorted values
-    km_tile_sums_kernel<<<(int)p.ntiles, 256, 0, st>>>(xs, m, tsum);
-    km_scan_tiles_kernel<<<1, 1024, 0, st>>>(tsum, p.ntiles);
-    km_prefix_kernel<<<(int)p.ntiles, 256, 0, st>>>(xs, m, tsum, P);
+    km_tile_sums_kernel<<<(int)p.ntiles, 256, 0, st>>>(p.xs, m, p.tsum);
+    km_scan_tiles_kernel<<<1, 1024, 0, st>>>(p.tsum, p.ntiles);
+    km_prefix_kernel<<<(int)p.ntiles, 256, 0, st>>>(p.xs, m, p.tsum, p.P);
     KmLloydBufs B;
-    double *lb = reinterpret_cast<double *>(ws + p.off_lloyd);
+    double *lb = p.lloyd;
     B.c = lb; B.cnew = lb + k; B.sums = lb + 2 * (size_t)k; B.counts = lb + 3 * (size_t)k; B.cfinal = lb + 4 * (size_t)k;
     B.maxval = lb + 5 * (size_t)k;
     B.hiS = reinterpret_cast<int64_t *>(lb + 6 * (size_t)k);
     B.lo = B.hiS + k; B.hi = B.lo + k; B.plo = B.hi + k; B.phi = B.plo + k; B.rl = B.phi + k; B.rh = B.rl + k;
     B.ord = reinterpret_cast<int32_t *>(B.rh + k);
-    km_lloyd_kernel<<<1, 1024, 0, st>>>(xs, P, m, k, max_iter, state, seeds_x, B, d_info, l_xtop, l_nsb, l_xtop2, l_n2, l_s2);
-    km_assign_kernel<<<stream_grid, 256, 0, st>>>(d_values, m, k, state, B.maxval, B.cfinal, B.ord, d_quantized, d_centers);
+    km_lloyd_kernel<<<1, 1024, 0, st>>>(p.xs, p.P, m, k, max_iter, p.state, p.seeds_x, B, d_info, l_xtop, l_nsb, l_xtop2, l_n2, l_s2);
+    km_assign_kernel<<<stream_grid, 256, 0, st>>>(d_values, m, k, p.state, B.maxval, B.cfinal, B.ord, d_quantized, d_centers);
     GRX_LAUNCH_CHECK();
     return GRX_OK;
 }

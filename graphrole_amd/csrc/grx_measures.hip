@@ -29,27 +29,15 @@ struct PowerWs {
     int32_t *ctrl;
 };
 
-size_t power_ws_bytes(int64_t n)
+PowerWs lay_out(GrxCarve &c, int64_t n)
 {
-    const size_t vec = grx_align_up((size_t)(n > 0 ? n : 1) * 8, 256);
-    return 7 * vec + grx_align_up(3 * MS_MAX_WG * 8, 256) + 256 + 256;
-}
-
-PowerWs carve(void *base, int64_t n)
-{
-    char *p = reinterpret_cast<char *>(base);
-    const size_t vec = grx_align_up((size_t)(n > 0 ? n : 1) * 8, 256);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
     PowerWs w;
-    w.x[0] = reinterpret_cast<double *>(p); p += vec;
-    w.x[1] = reinterpret_cast<double *>(p); p += vec;
-    w.y[0] = reinterpret_cast<double *>(p); p += vec;
-    w.y[1] = reinterpret_cast<double *>(p); p += vec;
-    w.z = reinterpret_cast<double *>(p); p += vec;
-    w.sinv = reinterpret_cast<double *>(p); p += vec;
-    w.hacc = reinterpret_cast<double *>(p); p += vec;
-    w.part = reinterpret_cast<double *>(p); p += grx_align_up(3 * MS_MAX_WG * 8, 256);
-    w.scal = reinterpret_cast<double *>(p); p += 256;
-    w.ctrl = reinterpret_cast<int32_t *>(p);
+    double **vectors[] = {&w.x[0], &w.x[1], &w.y[0], &w.y[1], &w.z, &w.sinv, &w.hacc};
+    for (double **v : vectors) *v = c.take<double>(nn);
+    w.part = c.take<double>(3 * MS_MAX_WG);
+    w.scal = c.take<double>(SC_COUNT);
+    w.ctrl = c.take<int32_t>(CT_COUNT);
     return w;
 }
 
@@ -274,10 +262,10 @@ int power_run(bool pagerank, int64_t n, const int64_t *d_row_ptr, const int32_t 
     GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows), "power iteration: hub list");
     GRX_REQUIRE(max_iter >= 0, "power iteration: max_iter must be >= 0");
     GRX_REQUIRE(tol >= 0.0, "power iteration: tol must be >= 0");
-    GRX_REQUIRE(ws_bytes >= power_ws_bytes(n), "power iteration: workspace %zu bytes, need %zu", ws_bytes,
-                power_ws_bytes(n));
+    GrxCarve c(d_ws);
+    const PowerWs ws = lay_out(c, n);
+    GRX_REQUIRE(ws_bytes >= c.used, "power iteration: workspace %zu bytes, need %zu", ws_bytes, c.used);
     hipStream_t st = grx_stream(stream);
-    const PowerWs ws = carve(d_ws, n);
     const int64_t hub_degree = (int64_t)GRX_HUB_FACTOR * lanes_per_row;
     const int rgrid = (int)grx_grid(n, MS_BLOCK / lanes_per_row, MS_MAX_WG);
     const int egrid = (int)grx_grid(n, MS_BLOCK, MS_MAX_WG);
@@ -417,8 +405,8 @@ __global__ __launch_bounds__(MS_BLOCK) void local_loops_kernel(int64_t n, const 
 
 extern "C" {
 
-size_t grx_pagerank_workspace_bytes(int64_t n) { return power_ws_bytes(n); }
-size_t grx_eigenvector_centrality_workspace_bytes(int64_t n) { return power_ws_bytes(n); }
+size_t grx_pagerank_workspace_bytes(int64_t n) { return grx_carve_bytes(lay_out, n); }
+size_t grx_eigenvector_centrality_workspace_bytes(int64_t n) { return grx_carve_bytes(lay_out, n); }
 
 int grx_pagerank(int64_t n, const int64_t *d_in_row_ptr, const int32_t *d_in_col, const double *d_in_w,
                  const double *d_out_weight, const int32_t *d_hub_rows, int64_t n_hub_rows, int lanes_per_row,

@@ -412,23 +412,24 @@ __global__ __launch_bounds__(256) void q_assign_big_kernel(const double *__restr
 
 struct QuantPlan {
     int64_t ntiles;
-    size_t off_sorted, off_P, off_P2, off_G, off_tsum, off_ce, off_arg, off_edges, off_bounds, off_nb, off_cell, off_D,
-        off_big, off_sort_ws, total;
     int64_t kmax;
     int cell_cap;          // micro-cells of the DP stage: Q_CELLS, or QC_BIG when every one of <= QC_BIG values is a cell
+    double *sorted, *P, *P2, *G, *tsum, *bounds, *cell, *D;
+    int64_t *ce, *edges, *big;                               // big: raw edges / running edges / new edges
+    int32_t *arg;
+    int *nb;
+    char *sort_ws;                                           // of grx_internal_sort_columns, one column of m
 };
 
-QuantPlan q_plan(int64_t m)
+QuantPlan q_plan(GrxCarve &c, int64_t m)
 {
     QuantPlan p;
     p.ntiles = grx_ceil_div(m, Q_TILE);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += grx_align_up(bytes, 256); return at; };
-    p.off_sorted = take((size_t)m * 8);
-    p.off_P = take((size_t)(m + 1) * 8);
-    p.off_P2 = take((size_t)(m + 1) * 8);
-    p.off_G = take((size_t)(m + 1) * 8);
-    p.off_tsum = take((size_t)p.ntiles * 3 * 8);
+    p.sorted = c.take<double>(m);
+    p.P = c.take<double>(m + 1);
+    p.P2 = c.take<double>(m + 1);
+    p.G = c.take<double>(m + 1);
+    p.tsum = c.take<double>(p.ntiles * 3);
     // tables of the many-level path are sized by the largest admissible level count (n_bins <= m)
     p.kmax = m < Q_BIG_MAX_BINS ? m : Q_BIG_MAX_BINS;
     if (p.kmax < Q_MAX_BINS) p.kmax = Q_MAX_BINS;
@@ -436,16 +437,15 @@ QuantPlan q_plan(int64_t m)
     // (k = 2**int(log2(m))) and r x F <= 16 x 480 values, where no density-based start is any good
     p.cell_cap = (m > Q_CELLS && m <= QC_BIG) ? QC_BIG : Q_CELLS;
     const size_t layers = (p.cell_cap == QC_BIG) ? (size_t)m : (size_t)Q_CELLS;
-    p.off_ce = take((size_t)(p.cell_cap + 2) * 8);
-    p.off_arg = take(layers * (size_t)(p.cell_cap + 1) * 4);
-    p.off_edges = take((size_t)(p.kmax + 1) * 8);
-    p.off_bounds = take((size_t)p.kmax * 8);
-    p.off_big = take((size_t)(p.kmax + 2) * 8 * 3);        // raw edges / running edges / new edges
-    p.off_nb = take(256);
-    p.off_cell = take((size_t)3 * (p.cell_cap + 1) * 8);
-    p.off_D = take((size_t)2 * (p.cell_cap + 1) * 8);
-    p.off_sort_ws = take(grx_sort_workspace_bytes(m, 1));
-    p.total = o;
+    p.ce = c.take<int64_t>(p.cell_cap + 2);
+    p.arg = c.take<int32_t>(layers * (size_t)(p.cell_cap + 1));
+    p.edges = c.take<int64_t>(p.kmax + 1);
+    p.bounds = c.take<double>(p.kmax);
+    p.big = c.take<int64_t>((size_t)(p.kmax + 2) * 3);
+    p.nb = c.take<int>(64);
+    p.cell = c.take<double>((size_t)3 * (p.cell_cap + 1));
+    p.D = c.take<double>((size_t)2 * (p.cell_cap + 1));
+    p.sort_ws = c.take<char>(grx_sort_workspace_bytes(m, 1));
     return p;
 }
 
@@ -453,10 +453,7 @@ QuantPlan q_plan(int64_t m)
 
 extern "C" {
 
-size_t grx_lloyd_max_workspace_bytes(int64_t m)
-{
-    return q_plan(m < 1 ? 1 : m).total;
-}
+size_t grx_lloyd_max_workspace_bytes(int64_t m) { return grx_carve_bytes(q_plan, m < 1 ? 1 : m); }
 
 int grx_lloyd_max(int64_t m, const double *d_values, int n_bins, int max_iter, double *d_quantized,
                   double *d_centers, int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream)
@@ -470,59 +467,48 @@ int grx_lloyd_max(int64_t m, const double *d_values, int n_bins, int max_iter, d
     }
     GRX_REQUIRE(m < ((int64_t)1 << 31), "grx_lloyd_max: m must be < 2^31");
     GRX_REQUIRE(d_values && d_quantized && d_centers && d_info && d_workspace, "grx_lloyd_max: NULL pointer");
-    const QuantPlan p = q_plan(m);
-    if (workspace_bytes < p.total) {
-        grx_set_error("grx_lloyd_max: workspace %zu < %zu", workspace_bytes, p.total);
+    GrxCarve c(d_workspace);
+    const QuantPlan p = q_plan(c, m);
+    if (workspace_bytes < c.used) {
+        grx_set_error("grx_lloyd_max: workspace %zu < %zu", workspace_bytes, c.used);
         return GRX_ERR_WORKSPACE;
     }
     hipStream_t st = grx_stream(stream);
-    char *ws = reinterpret_cast<char *>(d_workspace);
-    double *sorted = reinterpret_cast<double *>(ws + p.off_sorted);
-    double *P = reinterpret_cast<double *>(ws + p.off_P);
-    double *P2 = reinterpret_cast<double *>(ws + p.off_P2);
-    double *Gp = reinterpret_cast<double *>(ws + p.off_G);
-    double *tsum = reinterpret_cast<double *>(ws + p.off_tsum);
-    int64_t *ce = reinterpret_cast<int64_t *>(ws + p.off_ce);
-    int32_t *arg = reinterpret_cast<int32_t *>(ws + p.off_arg);
-    int64_t *edges = reinterpret_cast<int64_t *>(ws + p.off_edges);
-    double *bounds = reinterpret_cast<double *>(ws + p.off_bounds);
-    int *nb = reinterpret_cast<int *>(ws + p.off_nb);
-    double *cell = reinterpret_cast<double *>(ws + p.off_cell);
-    double *Dbuf = reinterpret_cast<double *>(ws + p.off_D);
-    int rc = grx_internal_sort_columns(m, 1, d_values, m, sorted, m, ws + p.off_sort_ws, st);
+    int rc = grx_internal_sort_columns(m, 1, d_values, m, p.sorted, m, p.sort_ws, st);
     if (rc != GRX_OK) return rc;
     {
         GRX_PROF(GRX_K_QUANT, st);
-        q_tile_sums_kernel<<<(int)p.ntiles, 256, 0, st>>>(sorted, m, tsum);
-        q_scan_tiles_kernel<<<1, 64, 0, st>>>(tsum, p.ntiles);
-        q_prefix_kernel<<<(int)p.ntiles, 256, 0, st>>>(sorted, m, tsum, P, P2, Gp);
-        int64_t *raw = reinterpret_cast<int64_t *>(ws + p.off_big);
-        int64_t *hi = raw + (p.kmax + 2), *nh = hi + (p.kmax + 2);
+        q_tile_sums_kernel<<<(int)p.ntiles, 256, 0, st>>>(p.sorted, m, p.tsum);
+        q_scan_tiles_kernel<<<1, 64, 0, st>>>(p.tsum, p.ntiles);
+        q_prefix_kernel<<<(int)p.ntiles, 256, 0, st>>>(p.sorted, m, p.tsum, p.P, p.P2, p.G);
+        int64_t *raw = p.big, *hi = raw + (p.kmax + 2), *nh = hi + (p.kmax + 2);
         if (n_bins <= Q_MAX_BINS || m <= QC_BIG) {
             // exact start: dynamic programming over the micro-cells (every value its own cell when m <= 8192)
             const int cs = p.cell_cap + 1;
-            q_cells_kernel<<<1, Q_CELLS, 0, st>>>(Gp, m, p.cell_cap, ce, nb);
-            q_dp_init_kernel<<<(p.cell_cap + 256) / 256, 256, 0, st>>>(ce, nb, P, P2, cell, Dbuf, cs);
+            q_cells_kernel<<<1, Q_CELLS, 0, st>>>(p.G, m, p.cell_cap, p.ce, p.nb);
+            q_dp_init_kernel<<<(p.cell_cap + 256) / 256, 256, 0, st>>>(p.ce, p.nb, p.P, p.P2, p.cell, p.D, cs);
             for (int j = 0; j < n_bins; ++j) {
-                double *Dprev = Dbuf + (size_t)(j & 1) * cs;
-                double *Dcur = Dbuf + (size_t)((j + 1) & 1) * cs;
-                q_dp_layer_kernel<<<(cs + 3) / 4, 256, 0, st>>>(nb, j, n_bins, cell, Dprev, Dcur, arg, cs);
+                double *Dprev = p.D + (size_t)(j & 1) * cs;
+                double *Dcur = p.D + (size_t)((j + 1) & 1) * cs;
+                q_dp_layer_kernel<<<(cs + 3) / 4, 256, 0, st>>>(p.nb, j, n_bins, p.cell, Dprev, Dcur, p.arg, cs);
             }
-            q_dp_backtrack_kernel<<<1, 64, 0, st>>>(ce, nb, n_bins, arg, edges, cs);
+            q_dp_backtrack_kernel<<<1, 64, 0, st>>>(p.ce, p.nb, n_bins, p.arg, p.edges, cs);
         } else {
-            q_cells_big_kernel<<<1, 1024, 0, st>>>(Gp, m, n_bins, raw, edges);
+            q_cells_big_kernel<<<1, 1024, 0, st>>>(p.G, m, n_bins, raw, p.edges);
         }
         if (n_bins > Q_MAX_BINS) {
-            q_lloyd_big_kernel<<<1, 1024, 0, st>>>(sorted, m, P, n_bins, max_iter, edges, d_centers, hi, nh, bounds, d_info);
+            q_lloyd_big_kernel<<<1, 1024, 0, st>>>(p.sorted, m, p.P, n_bins, max_iter, p.edges, d_centers, hi, nh,
+                                                   p.bounds, d_info);
             const int64_t want_big = grx_ceil_div(m, 256 * 4);
             q_assign_big_kernel<<<(int)(want_big > 2048 ? 2048 : want_big), 256, 0, st>>>(d_values, m, n_bins, d_centers,
-                                                                                        bounds, d_quantized);
+                                                                                        p.bounds, d_quantized);
             GRX_LAUNCH_CHECK();
             return GRX_OK;
         }
-        q_lloyd_kernel<<<1, Q_MAX_BINS, 0, st>>>(sorted, m, P, n_bins, max_iter, edges, d_centers, bounds, d_info);
+        q_lloyd_kernel<<<1, Q_MAX_BINS, 0, st>>>(p.sorted, m, p.P, n_bins, max_iter, p.edges, d_centers, p.bounds,
+                                                 d_info);
         const int64_t want = grx_ceil_div(m, 256 * 4);
-        q_assign_kernel<<<(int)(want > 2048 ? 2048 : want), 256, 0, st>>>(d_values, m, n_bins, d_centers, bounds,
+        q_assign_kernel<<<(int)(want > 2048 ? 2048 : want), 256, 0, st>>>(d_values, m, n_bins, d_centers, p.bounds,
                                                                           d_quantized);
     }
     GRX_LAUNCH_CHECK();

@@ -316,21 +316,23 @@ void sim_plan(int64_t n, int64_t nq, int segments, int *served, int64_t *tiles_p
     *served = (int)grx_ceil_div(tiles, *tiles_per_seg);
 }
 
-struct SimLayout { size_t xn, qn, part_key, part_idx, total; };
+struct SimLayout {
+    double *xn, *qn, *part_key;
+    int32_t *part_idx;                                       // the two part_ lists are empty when one segment serves
+};
 
-SimLayout sim_layout(int64_t n, int64_t nq, int c, int k, int segments)
+SimLayout sim_layout(GrxCarve &cv, int64_t n, int64_t nq, int c, int k, int segments)
 {
     int served = 1;
     int64_t tps = 0;
     sim_plan(n, nq, segments, &served, &tps);
     const size_t cp = (size_t)sim_padded(c);
-    SimLayout L;
-    L.xn = 0;
-    L.qn = L.xn + grx_align_up((size_t)n * cp * sizeof(double), 256);
-    L.part_key = L.qn + grx_align_up((size_t)nq * cp * sizeof(double), 256);
     const size_t lists = served > 1 ? (size_t)served * k * nq : 0;
-    L.part_idx = L.part_key + grx_align_up(lists * sizeof(double), 256);
-    L.total = L.part_idx + grx_align_up(lists * sizeof(int32_t), 256);
+    SimLayout L;
+    L.xn = cv.take<double>((size_t)n * cp);
+    L.qn = cv.take<double>((size_t)nq * cp);
+    L.part_key = cv.take<double>(lists);
+    L.part_idx = cv.take<int32_t>(lists);
     return L;
 }
 
@@ -363,7 +365,7 @@ bool sim_valid_sizes(int64_t n, int64_t nq, int c, int k, int segments)
 extern "C" size_t grx_similar_rows_workspace_bytes(int64_t n, int64_t nq, int c, int k, int segments)
 {
     if (!sim_valid_sizes(n, nq, c, k, segments) || n == 0 || nq == 0) return 0;
-    return sim_layout(n, nq, c, k, segments).total;
+    return grx_carve_bytes(sim_layout, n, nq, c, k, segments);
 }
 
 extern "C" int grx_similar_rows(int64_t n, int c, const double *d_X, int64_t ldx, int64_t nq, const double *d_Q,
@@ -393,15 +395,14 @@ extern "C" int grx_similar_rows(int64_t n, int c, const double *d_X, int64_t ldx
         return GRX_OK;
     }
     GRX_REQUIRE(d_X && d_Q && d_index && d_score && d_workspace, "grx_similar_rows: null pointer");
-    const SimLayout L = sim_layout(n, nq, c, k, segments);
-    GRX_REQUIRE(workspace_bytes >= L.total, "grx_similar_rows: workspace of %zu bytes, %zu needed "
-                "(grx_similar_rows_workspace_bytes)", workspace_bytes, L.total);
+    GrxCarve cv(d_workspace);
+    const SimLayout L = sim_layout(cv, n, nq, c, k, segments);
+    GRX_REQUIRE(workspace_bytes >= cv.used, "grx_similar_rows: workspace of %zu bytes, %zu needed "
+                "(grx_similar_rows_workspace_bytes)", workspace_bytes, cv.used);
 
     const bool cosine = metric == GRX_SIMILARITY_COSINE;
     const int cp = sim_padded(c);
-    char *ws = static_cast<char *>(d_workspace);
-    double *Xn = reinterpret_cast<double *>(ws + L.xn);
-    double *Qn = reinterpret_cast<double *>(ws + L.qn);
+    double *Xn = L.xn, *Qn = L.qn;
     sim_prepare_kernel<<<grx_grid(n, SIM_BLOCK, 2048), SIM_BLOCK, 0, st>>>(n, c, cp, d_X, ldx, cosine, Xn);
     if (d_Q == d_X && ldq == ldx && nq == n)
         Qn = Xn;                                                // the rows query themselves: one copy
@@ -421,8 +422,8 @@ extern "C" int grx_similar_rows(int64_t n, int c, const double *d_X, int64_t ldx
     A.out_score = d_score;
     A.ld_out = ld_out;
     if (A.segments > 1) {
-        A.part_key = reinterpret_cast<double *>(ws + L.part_key);
-        A.part_idx = reinterpret_cast<int32_t *>(ws + L.part_idx);
+        A.part_key = L.part_key;
+        A.part_idx = L.part_idx;
     }
     const dim3 grid((unsigned)grx_ceil_div(nq, SIM_TQ), (unsigned)A.segments);
     switch (cp) {

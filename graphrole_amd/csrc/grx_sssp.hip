@@ -68,27 +68,21 @@ int choose_batch(int64_t n, int batch, int64_t n_sources)
     return s;
 }
 
-size_t ws_bytes(int64_t n, int S)
-{
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    return 2 * grx_align_up(nn * (size_t)S * 8, 256) + grx_align_up(nn * 4, 256) + 256;
-}
-
 struct SpWs {
     double *d0, *d1;
     int32_t *stamp;
     int32_t *ctrl;
 };
 
-SpWs carve(void *base, int64_t n, int S)
+// the workspace of batch width S, sized (c.base == NULL) and carved by the same walk
+SpWs lay_out(GrxCarve &c, int64_t n, int S)
 {
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    char *p = reinterpret_cast<char *>(base);
     SpWs ws;
-    ws.d0 = reinterpret_cast<double *>(p); p += grx_align_up(nn * (size_t)S * 8, 256);
-    ws.d1 = reinterpret_cast<double *>(p); p += grx_align_up(nn * (size_t)S * 8, 256);
-    ws.stamp = reinterpret_cast<int32_t *>(p); p += grx_align_up(nn * 4, 256);
-    ws.ctrl = reinterpret_cast<int32_t *>(p);
+    ws.d0 = c.take<double>(nn * (size_t)S);
+    ws.d1 = c.take<double>(nn * (size_t)S);
+    ws.stamp = c.take<int32_t>(nn);
+    ws.ctrl = c.take<int32_t>(GRX_CTRL_MAX_WORDS);
     return ws;
 }
 
@@ -210,7 +204,7 @@ extern "C" {
 
 size_t grx_weighted_distances_workspace_bytes(int64_t n, int batch, int64_t n_sources)
 {
-    return ws_bytes(n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources));
+    return grx_carve_bytes(lay_out, n, choose_batch(n, sp_valid_batch(batch) ? batch : 0, n_sources));
 }
 
 int grx_weighted_distances(int64_t n, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_w,
@@ -227,14 +221,15 @@ int grx_weighted_distances(int64_t n, const int64_t *d_row_ptr, const int32_t *d
     GRX_REQUIRE(!d_dist || ld_dist >= n, "grx_weighted_distances: ld_dist = %lld below n = %lld", (long long)ld_dist,
                 (long long)n);
     const int S = choose_batch(n, batch, n_sources);
-    GRX_REQUIRE(workspace_bytes >= ws_bytes(n, S), "grx_weighted_distances: workspace %zu bytes, need %zu",
-                workspace_bytes, ws_bytes(n, S));
+    GrxCarve c(d_workspace);
+    const SpWs ws = lay_out(c, n, S);
+    GRX_REQUIRE(workspace_bytes >= c.used, "grx_weighted_distances: workspace %zu bytes, need %zu", workspace_bytes,
+                c.used);
     GRX_REQUIRE(d_row_ptr && d_col && d_reach && d_dsum && d_harmonic && d_far && d_workspace,
                 "grx_weighted_distances: null pointer");
     GRX_REQUIRE(lanes_per_row >= 1, "grx_weighted_distances: lanes_per_row must be >= 1");
     GRX_REQUIRE(n_hub_rows >= 0 && (n_hub_rows == 0 || d_hub_rows), "grx_weighted_distances: hub list");
     hipStream_t st = grx_stream(stream);
-    const SpWs ws = carve(d_workspace, n, S);
     const Args a{n, d_row_ptr, d_col, d_w, d_hub_rows, n_hub_rows, (int64_t)GRX_HUB_FACTOR * lanes_per_row,
                  d_sources, n_sources, d_reach, d_dsum, d_harmonic, d_far, d_source_ecc, d_dist, ld_dist};
     grx_fill64(reinterpret_cast<uint64_t *>(d_reach), n, 0, st);

@@ -15,6 +15,7 @@
 // same bits on every run.
 #include "grx_common.h"
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <utility>
@@ -136,23 +137,25 @@ constexpr std::array<BlockKernel, sizeof...(Rs)> block_table(std::integer_sequen
 }
 const auto BLOCK_KERNELS = block_table(std::make_integer_sequence<int, GRX_MAX_ROLES>{});
 
-struct TransformLayout { size_t shared, q, h, b, stats, partial, scalars, total; int64_t ldq; };
+struct TransformLayout {
+    char *shared;                                            // the projection, then the direct residual passes
+    size_t shared_bytes;
+    double *q, *h, *b, *stats, *partial, *scal;
+    int64_t ldq;
+};
 
-TransformLayout transform_layout(int64_t n, int F, int r)
+TransformLayout transform_layout(GrxCarve &c, int64_t n, int F, int r)
 {
     TransformLayout L;
-    const size_t p = grx_project_workspace_bytes(n, r), m = grx_nmf_workspace_bytes(n, F, r);
     L.ldq = (int64_t)grx_align_up((size_t)(n > 0 ? n : 1), 32);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += grx_align_up(bytes, 256); return at; };
-    L.shared = take(p > m ? p : m);                           // the projection, then the direct residual passes
-    L.q = take((size_t)r * (size_t)L.ldq * 8);
-    L.h = take((size_t)r * F * 8);
-    L.b = take((size_t)r * r * 8);
-    L.stats = take((size_t)r * 4 * 8);
-    L.partial = take((size_t)2 * TR_MAX_GRID * 8);
-    L.scalars = take((size_t)TS_COUNT * 8);
-    L.total = o;
+    L.shared_bytes = std::max(grx_project_workspace_bytes(n, r), grx_nmf_workspace_bytes(n, F, r));
+    L.shared = c.take<char>(L.shared_bytes);
+    L.q = c.take<double>((size_t)r * (size_t)L.ldq);
+    L.h = c.take<double>((size_t)r * F);
+    L.b = c.take<double>((size_t)r * r);
+    L.stats = c.take<double>((size_t)r * 4);
+    L.partial = c.take<double>((size_t)2 * TR_MAX_GRID);
+    L.scal = c.take<double>(TS_COUNT);
     return L;
 }
 
@@ -185,7 +188,7 @@ size_t grx_nmf_transform_workspace_bytes(int64_t n, int F, int r)
     if (F < 1) F = 1;
     if (r < 1) r = 1;
     if (r > GRX_MAX_ROLES) r = GRX_MAX_ROLES;
-    return transform_layout(n, F, r).total;
+    return grx_carve_bytes(transform_layout, n, F, r);
 }
 
 int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, const double *h_H, double tol, int max_iter,
@@ -199,16 +202,13 @@ int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, c
     info->err_init = info->err_last = info->x_sq_norm = 0.0;
     if (n == 0) return GRX_OK;
     GRX_REQUIRE(d_X && h_H && d_W && d_workspace, "grx_nmf_transform: NULL pointer");
-    const TransformLayout L = transform_layout(n, F, r);
-    if (workspace_bytes < L.total) {
-        grx_set_error("grx_nmf_transform: workspace %zu < %zu", workspace_bytes, L.total);
+    GrxCarve c(d_workspace);
+    const TransformLayout L = transform_layout(c, n, F, r);
+    if (workspace_bytes < c.used) {
+        grx_set_error("grx_nmf_transform: workspace %zu < %zu", workspace_bytes, c.used);
         return GRX_ERR_WORKSPACE;
     }
     hipStream_t st = grx_stream(stream);
-    char *ws = reinterpret_cast<char *>(d_workspace);
-    double *dQ = reinterpret_cast<double *>(ws + L.q), *dH = reinterpret_cast<double *>(ws + L.h);
-    double *dB = reinterpret_cast<double *>(ws + L.b), *dStats = reinterpret_cast<double *>(ws + L.stats);
-    double *partial = reinterpret_cast<double *>(ws + L.partial), *scal = reinterpret_cast<double *>(ws + L.scalars);
     if (!g_pinned.ptr) GRX_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&g_pinned.ptr), TS_COUNT * 8, hipHostMallocMapped));
     double *host = g_pinned.ptr;
 
@@ -222,29 +222,29 @@ int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, c
             for (int c = 0; c < F; ++c) s += h_H[(size_t)k * F + c] * h_H[(size_t)l * F + c];
             Bh[(size_t)k * r + l] = Bh[(size_t)l * r + k] = s;
         }
-    GRX_CHECK_HIP(hipMemcpyAsync(dH, h_H, (size_t)r * F * 8, hipMemcpyHostToDevice, st));
-    GRX_CHECK_HIP(hipMemcpyAsync(dB, Bh.data(), (size_t)r * r * 8, hipMemcpyHostToDevice, st));
+    GRX_CHECK_HIP(hipMemcpyAsync(L.h, h_H, (size_t)r * F * 8, hipMemcpyHostToDevice, st));
+    GRX_CHECK_HIP(hipMemcpyAsync(L.b, Bh.data(), (size_t)r * r * 8, hipMemcpyHostToDevice, st));
 
     const int grid = (int)grx_grid(n, TR_BLOCK, TR_MAX_GRID);
     {
         GRX_PROF(GRX_K_TRANSFORM_NORMS, st);
-        transform_norms_kernel<<<grid, TR_BLOCK, 0, st>>>(n, F, d_X, ldx, partial);
+        transform_norms_kernel<<<grid, TR_BLOCK, 0, st>>>(n, F, d_X, ldx, L.partial);
     }
     GRX_LAUNCH_CHECK();
-    transform_reduce_kernel<<<2, 64, 0, st>>>(partial, grid, scal + TS_SUM);
+    transform_reduce_kernel<<<2, 64, 0, st>>>(L.partial, grid, L.scal + TS_SUM);
     GRX_LAUNCH_CHECK();
-    GRX_TRY(grx_project(n, F, d_X, ldx, 0, n, Z.data(), r, dQ, L.ldq, dStats, ws + L.shared, L.q - L.shared, stream));
+    GRX_TRY(grx_project(n, F, d_X, ldx, 0, n, Z.data(), r, L.q, L.ldq, L.stats, L.shared, L.shared_bytes, stream));
 
     const BlockKernel kernel = BLOCK_KERNELS[r - 1];
     const double x_size = (double)n * (double)F;
     auto block = [&](int iters, int init, bool want_terms) -> int {
         {
             GRX_PROF(GRX_K_NMF_TRANSFORM_BLOCK, st);
-            kernel<<<grid, TR_BLOCK, 0, st>>>(n, dQ, L.ldq, d_W, ldw, dB, iters, init, scal, x_size, partial);
+            kernel<<<grid, TR_BLOCK, 0, st>>>(n, L.q, L.ldq, d_W, ldw, L.b, iters, init, L.scal, x_size, L.partial);
         }
         GRX_LAUNCH_CHECK();
         if (want_terms) {
-            transform_reduce_kernel<<<1, 64, 0, st>>>(partial, grid, scal + TS_TERMS);
+            transform_reduce_kernel<<<1, 64, 0, st>>>(L.partial, grid, L.scal + TS_TERMS);
             GRX_LAUNCH_CHECK();
         }
         return GRX_OK;
@@ -255,9 +255,9 @@ int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, c
     auto error_of = [&](double terms, double *err) -> int {
         const double sq = xx + terms;
         if (sq > 1e-8 * xx) { *err = std::sqrt(sq); return GRX_OK; }
-        GRX_TRY(grx_nmf_residual(n, F, r, d_X, ldx, d_W, ldw, 0, n, dH, scal + TS_DIRECT, ws + L.shared, L.q - L.shared,
+        GRX_TRY(grx_nmf_residual(n, F, r, d_X, ldx, d_W, ldw, 0, n, L.h, L.scal + TS_DIRECT, L.shared, L.shared_bytes,
                                  stream));
-        GRX_TRY(grx_fetch_begin(host + TS_DIRECT, scal + TS_DIRECT, 8, st));
+        GRX_TRY(grx_fetch_begin(host + TS_DIRECT, L.scal + TS_DIRECT, 8, st));
         GRX_TRY(grx_fetch_wait(st));
         *err = std::sqrt(host[TS_DIRECT]);
         info->direct_residuals += 1;
@@ -266,7 +266,7 @@ int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, c
 
     // W0 and its error (_nmf.py:826) -- one read-back for sum(X), ||X||^2 and the shares at W0
     GRX_TRY(block(0, 1, true));
-    GRX_TRY(grx_fetch_begin(host, scal, 3 * 8, st));
+    GRX_TRY(grx_fetch_begin(host, L.scal, 3 * 8, st));
     GRX_TRY(grx_fetch_wait(st));
     xx = host[TS_SQ];
     info->x_sq_norm = xx;
@@ -286,7 +286,7 @@ int grx_nmf_transform(int64_t n, int F, int r, const double *d_X, int64_t ldx, c
         GRX_TRY(block(step, 0, check));
         n_iter += step;
         if (!check) continue;
-        GRX_TRY(grx_fetch_begin(host + TS_TERMS, scal + TS_TERMS, 8, st));
+        GRX_TRY(grx_fetch_begin(host + TS_TERMS, L.scal + TS_TERMS, 8, st));
         GRX_TRY(grx_fetch_wait(st));
         double err = 0.0;
         GRX_TRY(error_of(host[TS_TERMS], &err));
